@@ -24,8 +24,21 @@ runs at any world size through the same RCCL exchange):
                k bad items of every SURVEY §8(d) kind (bisection fallback each
                step), plus AggregateVerify with N = 128 .. 8,192 distinct
                messages as secondary figures.
-The c2 line also carries the registry-load figure (`registry_load`: bls_registry_load of the 2^20 compressed
-keys the passes then read, keys/s), a C3 epoch-replay figure (`c3`), a C4 figure (`c4`: one 125,000-Verify shard
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: setup, one priming
+pass per job slot, W warm-up steps, the N timed steps, the output dump when --dump-outputs is given, and the
+result line.  Everything below that is measured or checked beside the headline (the registry-load figure, the
+C3 / C4 / C5 figures, AggregateVerify, per-kernel times and roofline, the host-buffer rate, per-call latency,
+the parity sample, the CPU baseline) runs only with --full, where the --no-* / --cN-steps options still switch
+the single legs.
+
+--dump-outputs DIR writes what the timed path handed back in its last timed step as DIR/<name>.npy (float32):
+`verdicts` (one 0/1 per item of the batch, as ResidentFavBatch.verdicts() returns them) and `batch_ok` (the
+pass's batch check, as run_pipelined returns it).  Inputs are a function of the arguments alone -- the
+random-linear-combination seed of every pass is SHA256("rlc"||seed||rank||pass counter) -- so two builds run
+with the same arguments can be compared output for output.  Ranks above 0 write <name>.rank<r>.npy.
+
+With --full the c2 line also carries the registry-load figure (`registry_load`: bls_registry_load of the 2^20
+compressed keys the passes then read, keys/s), a C3 epoch-replay figure (`c3`), a C4 figure (`c4`: one 125,000-Verify shard
 per GPU, Verify/s), a C5 figure (`c5`: adversarial 1,024 x 512 batches with 8 bad items, FAV/s, plus
 AggregateVerify N = 128 / 1,024 / 8,192 in pairs/s) and, on rank 0, a
 parity sample (`parity`): an adversarial 1,024 x 512 slice with 8 bad items of
@@ -40,7 +53,7 @@ and every rank final-exponentiates the product.  torch.distributed (gloo) is
 only the control plane: rendezvous, the RCCL unique id, barriers, max over
 ranks.
 
-Roofline: after the timed region, a few passes run one batch at a time with
+Roofline (--full): after the timed region, a few passes run one batch at a time with
 per-kernel hipEvent timing (bls_profile_*), so each kernel's average is its
 own execution time (with five batches in flight a hipEvent pair also spans
 the wait for the queue and CUs); `roofline` uses those averages.
@@ -416,8 +429,9 @@ def run_c4(batch, ctx, timed, total: int, seed: int, rank: int, world: int, step
     idx, offs, msgs, sks, chunks, (lo, hi) = c4_shard(total, seed, rank, world)
     rb = batch.ResidentFavBatch(idx, offs, msgs, batch.sign_batch(sks, msgs, ctx=ctx), ctx=ctx, chunks=chunks)
     dt, oks = timed(rb, steps, warmup)
-    assert all(oks) and rb.verdicts().all(), "a valid C4 Verify was rejected"
-    return {"rb": rb, "dt": dt, "shard_items": hi - lo, "shard": [lo, hi], "chunks": chunks,
+    v = rb.verdicts()
+    assert all(oks) and v.all(), "a valid C4 Verify was rejected"
+    return {"rb": rb, "dt": dt, "last": (v, oks[-1]), "shard_items": hi - lo, "shard": [lo, hi], "chunks": chunks,
             "verify_s": round(total * steps / dt, 1), "ms_per_shard": round(dt / steps * 1e3, 3), "steps": steps}
 
 
@@ -434,9 +448,11 @@ def run_c5(batch, ctx, timed, n: int, bad: int, seed: int, rank: int, world: int
     rb = batch.ResidentFavBatch(idx2d.reshape(-1), offs, b"".join(msgs), bytes(sigs), ctx=ctx)
     dt, oks = timed(rb, steps, warmup)
     assert not any(oks) if plan else all(oks)
-    assert (rb.verdicts() == expect).all(), "adversarial verdicts differ from the construction"
+    v = rb.verdicts()
+    assert (v == expect).all(), "adversarial verdicts differ from the construction"
     checks, rounds = batch.fallback_stats(ctx=ctx)
-    out = {"rb": rb, "dt": dt, "items": B, "committee": n, "bad": len(plan), "bad_kinds": sorted(set(plan.values())),
+    out = {"rb": rb, "dt": dt, "last": (v, oks[-1]),
+           "items": B, "committee": n, "bad": len(plan), "bad_kinds": sorted(set(plan.values())),
            "fav_s": round(B * world * steps / dt, 1), "ms_per_batch": round(dt / steps * 1e3, 3), "steps": steps,
            "verdict_mismatches": 0, "fallback_last_step": {"fe_checks": checks, "bisection_rounds": rounds}}
     if aggregate_verify:  # AggregateVerify with N distinct messages (drop-in per call)
@@ -461,13 +477,14 @@ def run_c5(batch, ctx, timed, n: int, bad: int, seed: int, rank: int, world: int
     return out
 
 
-def registry_load_figure(ctx, reg_n: int, reps: int = 3) -> dict:
+def registry_load_figure(ctx, reg_n: int, reps: int = 3, figure: bool = True) -> dict | None:
     """SURVEY.md §8(d) registry load (specs/phase0/beacon-chain.md:787 reads state.validators[*].pubkey; deposits
     append, :2037-2062): decode + KeyValidate of reg_n compressed keys (pk_i = (i + 1) G1, made on the device)
     plus the two invalid keys the C5 kinds index and the 8 tests/golden/bls_formats.json key_validate fixtures,
     through bls_registry_load (host buffer in, validity mask out).  The table it leaves behind is the one the
     C2 / C3 passes then read, so every later verdict checks the decoded keys.  keys_s = API wall-clock
-    (PCIe-inclusive); kernel_keys_s = keys / k_key_validate's hipEvent time."""
+    (PCIe-inclusive); kernel_keys_s = keys / k_key_validate's hipEvent time.  figure=False (a plain run): one
+    load, mask checked, nothing timed per kernel and no figure returned."""
     import ctypes
 
     from bls_mi355x import batch
@@ -483,6 +500,10 @@ def registry_load_figure(ctx, reg_n: int, reps: int = 3) -> dict:
     expect = np.concatenate([np.ones(reg_n, np.uint8), np.zeros(2, np.uint8),
                              np.array([1 if c["output"] else 0 for c in kv], np.uint8)])
     valid = np.zeros(n, dtype=np.uint8)
+    if not figure:
+        ctx.check(ctx.lib.bls_registry_load(ctx.h, data, n, valid.ctypes.data))
+        assert (valid == expect).all(), "registry load: KeyValidate mask differs from the construction / fixtures"
+        return None
     prof = batch.Profiler(ctx)
     ts = []
     for r in range(reps):
@@ -618,7 +639,16 @@ def main():
     ap.add_argument("--roofline-passes", type=int, default=5, help="one-batch-at-a-time passes timed per kernel")
     ap.add_argument("--no-percall", action="store_true", help="skip the drop-in per-call latency figures")
     ap.add_argument("--no-parity", action="store_true", help="skip the parity sample")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: registry-load, C3 / C4 / C5 and AggregateVerify "
+                         "figures, per-kernel times and roofline, host-buffer rate, per-call latency, parity sample, "
+                         "CPU baseline (each still switched off by its --no-* / --cN-steps 0 option)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline only
+        args.no_cpu = args.no_profile = args.no_e2e = args.no_percall = args.no_parity = True
+        args.c3_steps = args.c4_steps = args.c5_steps = 0
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
@@ -670,6 +700,23 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
+    passes = iter(range(1 << 62))
+
+    def rlc_seeds(k: int) -> list:
+        """A fresh random-linear-combination seed for each of the next k passes, a function of --seed, the rank and
+        the pass's number in this run: no two passes share one, and a rerun with the same arguments repeats them."""
+        return [hashlib.sha256(b"rlc" + args.seed.to_bytes(8, "little") + rank.to_bytes(4, "little")
+                               + next(passes).to_bytes(8, "little")).digest() for _ in range(k)]
+
+    def dump_outputs(verdicts, batch_ok) -> None:
+        """--dump-outputs: what the last timed pass handed back (B float32 verdicts: far below the 64 MB cap)."""
+        if not args.dump_outputs:
+            return
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = f".rank{rank}" if rank else ""
+        np.save(os.path.join(args.dump_outputs, f"verdicts{sfx}.npy"), np.asarray(verdicts, dtype=np.float32))
+        np.save(os.path.join(args.dump_outputs, f"batch_ok{sfx}.npy"), np.asarray([batch_ok], dtype=np.float32))
+
     def timed(rb, steps, warmup, depth=None):
         """warmup + `steps` timed passes of rb between barriers; max over ranks; every pass must pass.  Setup
         first: one pass on every job slot, so each slot's device scratch is allocated (hipMalloc) before the
@@ -677,12 +724,12 @@ def main():
         would land inside it)."""
         d = 1 if args.no_pipeline else (batch.FAV_DEPTH if depth is None else depth)
         prime = -(-batch.FAV_JOBS // rb.chunks) if d > 1 else 1  # passes covering every slot (a pass = `chunks` jobs)
-        rb.run_pipelined([os.urandom(32) for _ in range(prime)], depth=d, comm=comm)
+        rb.run_pipelined(rlc_seeds(prime), depth=d, comm=comm)
         if warmup:
-            rb.run_pipelined([os.urandom(32) for _ in range(warmup)], depth=d, comm=comm)
+            rb.run_pipelined(rlc_seeds(warmup), depth=d, comm=comm)
         barrier_sync()
         t0 = time.perf_counter()
-        oks = rb.run_pipelined([os.urandom(32) for _ in range(steps)], depth=d, comm=comm)
+        oks = rb.run_pipelined(rlc_seeds(steps), depth=d, comm=comm)
         barrier_sync()
         return max_over_ranks(time.perf_counter() - t0), oks
 
@@ -691,8 +738,10 @@ def main():
     extra = {}
     reg = batch.Registry(ctx)
     if args.config == "c2" and args.registry == REG_N and not args.no_regload:
-        # the registry the passes read is decoded from compressed keys (the §8(d) registry-load figure)
-        extra["registry_load"] = registry_load_figure(ctx, REG_N)
+        # the registry the passes read is decoded from compressed keys (--full: the §8(d) registry-load figure)
+        fig = registry_load_figure(ctx, REG_N, figure=args.full)
+        if fig is not None:
+            extra["registry_load"] = fig
     else:
         reg.generate(args.registry, first_sk=1)
         if args.registry == REG_N:
@@ -710,6 +759,7 @@ def main():
         assert all(oks), "a valid C2 batch failed the pairing check"
         v = rb.verdicts()
         assert v.all(), f"{(~v).sum()} valid aggregates rejected"
+        dump_outputs(v, oks[-1])
         units, unit, scaling = B * world, "FAV/s", "weak"
         workload = f"C2 sync-committee FastAggregateVerify: {B} aggregates x {n} pubkeys per GPU"
         ops_step = item_ops(n) * B * world + BATCH_OPS * world
@@ -719,7 +769,9 @@ def main():
         rb = batch.ResidentFavBatch(idx, offs, msgs, batch.sign_batch(sks, msgs, ctx=ctx), ctx=ctx)
         setup_s = time.perf_counter() - t_setup
         dt, oks = timed(rb, args.steps, args.warmup)
-        assert all(oks) and rb.verdicts().all()
+        v = rb.verdicts()
+        assert all(oks) and v.all()
+        dump_outputs(v, oks[-1])
         units, unit, scaling = C3_SLOTS * C3_PER_SLOT, "FAV/s", "strong"
         workload = (f"C3 mainnet epoch replay: {C3_SLOTS} slots x {C3_PER_SLOT} committees of {C3_N} over a "
                     f"2^20 registry, epoch sharded over {world} GPU(s), one RLC verdict per epoch")
@@ -728,6 +780,7 @@ def main():
     elif args.config == "c4":
         r4 = run_c4(batch, ctx, timed, args.c4_total, args.seed, rank, world, args.steps, args.warmup)
         rb, dt, B, chunks = r4.pop("rb"), r4.pop("dt"), r4["shard_items"], r4["chunks"]
+        dump_outputs(*r4.pop("last"))
         setup_s = time.perf_counter() - t_setup
         units, unit, scaling = args.c4_total, "Verify/s", "strong"
         workload = (f"C4 gossip firehose: {args.c4_total} single-signature Verify (pk_i = registry[i], distinct "
@@ -735,8 +788,9 @@ def main():
         ops_step = item_ops(1) * units + BATCH_OPS * chunks * world
     else:  # c5
         r5 = run_c5(batch, ctx, timed, n, args.c5_bad, args.seed, rank, world, args.registry, args.steps, args.warmup,
-                    aggregate_verify=rank == 0)
+                    aggregate_verify=args.full and rank == 0)
         rb, dt, B = r5.pop("rb"), r5.pop("dt"), r5["items"]
+        dump_outputs(*r5.pop("last"))
         setup_s = time.perf_counter() - t_setup
         units, unit, scaling = B * world, "FAV/s", "weak"
         workload = (f"C5 adversarial FAV batches: {B} x {n} per GPU with {args.c5_bad} bad items "
@@ -767,14 +821,14 @@ def main():
         if args.c4_steps > 0:  # one 125,000-Verify shard per GPU (the 8-GPU shard of 10^6)
             r4 = run_c4(batch, ctx, timed, C4_CHUNK * world, args.seed, rank, world, args.c4_steps, 1)
             r4.pop("rb").free()
-            r4.pop("dt")
+            r4.pop("dt"), r4.pop("last")
             r4["workload"] = f"{C4_CHUNK} single-signature Verify per GPU (pk_i = registry[i], distinct messages)"
             extra["c4"] = r4
         if args.c5_steps > 0:
             r5 = run_c5(batch, ctx, timed, n, args.c5_bad, args.seed, rank, world, args.registry, args.c5_steps, 1,
                         aggregate_verify=rank == 0)
             r5.pop("rb").free()
-            r5.pop("dt")
+            r5.pop("dt"), r5.pop("last")
             r5["workload"] = f"1024 x {n} FAV per GPU with {args.c5_bad} bad items, bisection fallback every pass"
             extra["c5"] = r5
 
@@ -783,7 +837,7 @@ def main():
     if not args.no_profile and args.roofline_passes > 0 and rb is not None and rb.chunks == 1:
         prof = batch.Profiler(ctx)
         prof.start()
-        rb.run_pipelined([os.urandom(32) for _ in range(args.roofline_passes)], depth=1, comm=comm)
+        rb.run_pipelined(rlc_seeds(args.roofline_passes), depth=1, comm=comm)
         kern = prof.read()
         prof.stop()
 
@@ -860,6 +914,7 @@ def main():
     out = {
         "metric": METRIC, "value": round(value, 2), "unit": unit, "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": scaling,
+        "full": args.full,
         "vs_baseline": None, "dtype": "u32 (381-bit Montgomery Fp, radix-2^29 digits)",
         "data": "synthetic: registry sk_i=i+1 (2^20 keys, HBM), SHA256 messages, signatures made on device",
         "config": {"workload": workload, "config": args.config,

@@ -67,6 +67,15 @@ def test_launcher_dry_run_rank_envs(n):
     assert len({c["MASTER_PORT"] for c in ch}) == 1 and int(ch[0]["MASTER_PORT"]) > 0
 
 
+def test_launcher_hands_full_and_dump_outputs_to_the_ranks():
+    import json
+
+    p = _run_bench(["--gpus", "2", "--full", "--dump-outputs", "out", "--launch-dry-run"])
+    assert p.returncode == 0, p.stderr
+    cmd = json.loads(p.stdout.strip().splitlines()[-1])["launcher"]["cmd"]
+    assert cmd[-6:] == ["--gpus", "2", "--full", "--dump-outputs", "out", "--launch-dry-run"]
+
+
 def test_launcher_refuses_world_mismatch_and_missing_gpus():
     p = _run_bench(["--gpus", "2"], WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     assert p.returncode == 2 and "WORLD_SIZE=1" in p.stderr and "--gpus 2" in p.stderr

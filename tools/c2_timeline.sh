@@ -9,7 +9,7 @@ for kv in "$@"; do
   i=$((i+1))
   envs=""; [ "$kv" != base ] && envs="$kv"
   env $envs timeout -k 10 300 rocprofv3 --kernel-trace -d "$OUT/t$i" -o run -- \
-    python3 bench.py --steps 30 --warmup 2 --no-cpu --no-percall --no-parity --no-e2e --no-profile --no-regload \
+    python3 bench.py --full --steps 30 --warmup 2 --no-cpu --no-percall --no-parity --no-e2e --no-profile --no-regload \
     --c3-steps 0 --c4-steps 0 --c5-steps 0 > "$OUT/t$i.log" 2>&1 || { echo "[$kv] FAILED"; tail -5 "$OUT/t$i.log"; exit 1; }
   db=$(find "$OUT/t$i" -name '*.db' | head -n 1)
   echo "== [$kv] $(python3 -c "import json,sys; d=json.loads(open('$OUT/t$i.log').read().strip().splitlines()[-1]); print(d['value'])")"

@@ -7,7 +7,7 @@ R=$1; shift
 for r in $(seq 1 $R); do
   for v in "$@"; do
     lib=$PWD/exp_libs/lib_$v.so; [ "$v" = cur ] && lib=$PWD/eth-consensus-specs_amd/libblsmi355x.so
-    BLSMI355X_LIB=$lib timeout -k 10 120 python3 bench.py --config c5 --steps 20 --warmup 2 --no-cpu --no-percall \
+    BLSMI355X_LIB=$lib timeout -k 10 120 python3 bench.py --full --config c5 --steps 20 --warmup 2 --no-cpu --no-percall \
       --no-parity --no-profile > $OUT/$v.$r.json 2> $OUT/$v.$r.err || { echo "$v FAILED"; tail -3 $OUT/$v.$r.err; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/$v.$r.json')); print('$v', d['value'], d['ms_per_step'], d['fallback_last_step'])"
   done

@@ -10,7 +10,7 @@ for r in $(seq 1 $REPS); do
   for kv in "$@"; do
     i=$((i+1))
     envs=""; [ "$kv" != base ] && envs="$kv"
-    env $envs timeout -k 10 200 python3 bench.py --config $CFG --steps $STEPS --warmup 3 --no-cpu --no-percall --no-e2e \
+    env $envs timeout -k 10 200 python3 bench.py --full --config $CFG --steps $STEPS --warmup 3 --no-cpu --no-percall --no-e2e \
       --no-parity --roofline-passes 2 --no-regload > $OUT/k${i}_r$r.json 2> $OUT/k${i}_r$r.err \
       || { echo "[$kv] FAILED rc=$?"; tail -3 $OUT/k${i}_r$r.err | cut -c1-300; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/k${i}_r$r.json')); print('[$kv] r$r', d['value'])"
