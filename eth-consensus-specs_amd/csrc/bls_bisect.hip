@@ -1,6 +1,9 @@
 // Kernels of the bisection fallback of a failing FAV batch (bls_capi.hip fav_bisect), which reuses the batch's own
 // Miller kernels for its per-item values:
-//   k_neg_g1_comb_table  once per context: comb[256 w + d] = d 2^(8 w) (-G1), affine (d = 1 .. 255, w = 0 .. 7)
+//   k_neg_g1_comb_table  once per context: comb[256 w + d] = d 2^(8 w) (-G1) for w = 0 .. 3 and
+//                        comb[256 w + d] = phi(comb[256 (w - 4) + d]) = d 2^(8 (w - 4)) lambda (-G1) for w = 4 .. 7,
+//                        affine (d = 1 .. 255): the RLC scalar is r_i = a + b lambda, a its low and b its high 32
+//                        bits (bls_g1_endo.h), so window w of its 64 bits weighs 2^(8 w) or 2^(8 (w - 4)) lambda
 //   k_neg_rg1            -r_i G1 from the comb: eight complete mixed additions per item (fixed base, no doublings)
 //   k_verdicts_res       verdict = status && the item's leaf passed (or inherited its ancestors' pass)
 // The gated final-exponentiation checks of the tree levels are k_fe_check_gated (bls_fe.hip), the leaf and node
@@ -23,23 +26,26 @@ __global__ void __launch_bounds__(64) k_neg_g1_comb_table(G1A* tab) {
   const int w = t / COMB_D, d = t % COMB_D;
   G1A g = g1_generator();
   const G1Q A{fq_unpack(g.x), fq_unpack(fp_neg(g.y)), fq_unpack(FP_ONE)};
-  const uint64_t k = (uint64_t)d << (8 * w);
+  const uint32_t k = (uint32_t)d << (8 * (w & 3));
   G1Q R{fq_zero(), fq_unpack(FP_ONE), fq_zero()};
 #pragma unroll 1
-  for (int b = 63; b >= 0; --b) {  // complete formulas: the identity start and d = 0 need no special case
+  for (int b = 31; b >= 0; --b) {  // complete formulas: the identity start and d = 0 need no special case
     R = g1q_dbl(R);
-    if ((k >> b) & 1ull) R = g1q_add(R, A);
+    if ((k >> b) & 1u) R = g1q_add(R, A);
   }
   const Fp z = fq_pack(R.z);
   G1A o{fp_zero(), fp_zero(), true};
   if (!fp_is_zero(z)) {
     const Fp zi = fp_inv_sg_i(z);
-    o = G1A{fp_mul_i(fq_pack(R.x), zi), fp_mul_i(fq_pack(R.y), zi), false};
+    Fp x = fp_mul_i(fq_pack(R.x), zi);
+    if (w >= 4) x = fp_mul_i(x, FP_BETA);  // phi: the scalar's high half weighs lambda (bls_g1_endo.h)
+    o = G1A{x, fp_mul_i(fq_pack(R.y), zi), false};
   }
   tab[t] = o;
 }
 
-// -r_i G1 = sum_w d_w 2^(8 w) (-G1), r_i = sum_w d_w 2^(8 w): the table entries are affine, so each window is one
+// -r_i G1 = sum_w d_w comb[256 w + d_w], d_w the 8-bit windows of the 64 scalar bits (r_i = a + b lambda: windows
+// 0 .. 3 weigh 2^(8 w), windows 4 .. 7 weigh 2^(8 (w - 4)) lambda): the table entries are affine, so each window is one
 // complete mixed addition (RCB alg. 8, g1q_add_aff; the identity start needs no case) -- 8 x 12 products per item
 // where a double-and-add chain on -G1 would take ~64 doublings and ~32 additions.  Items with status 0 are skipped
 // (their leaf is 1 on both sides, bls_capi.hip fav_bisect).

@@ -1198,7 +1198,9 @@ static int fav_prepare(bls_ctx* ctx, const uint32_t* d_idx, const uint64_t* d_of
     ctx->err = "no registry loaded";
     return BLS_E_NOREG;
   }
-  // pairs 0 .. B: (r_i apk_i, H_i); pairs B .. B + 64: (-2^b G1, U_b), the MSM's bit-sums (bls_msm.hip)
+  // pairs 0 .. B: (r_i apk_i, H_i); pairs B .. B + 64: (-w_b G1, U_b), the MSM's bit-sums (bls_msm.hip).  The 64
+  // scalar bits read as r_i = a + b lambda (a the low, b the high half; lambda = -x^2 mod r, phi's eigenvalue on
+  // G1): bit b weighs w_b = 2^b below 32 and 2^(b - 32) lambda above, on both sides (bls_g1_endo.h, the comb)
   const size_t NP = B + MSM_UPAIRS;
   int *status, *gstat, *flag, *dstat;
   G1P *apka, *rpj;
@@ -1232,7 +1234,7 @@ static int fav_prepare(bls_ctx* ctx, const uint32_t* d_idx, const uint64_t* d_of
   SCR(S_SEED, 32, d_seed);
   Job& J = *ctx->j;
   hipStream_t st = J.stream, st2 = J.stream2, st3 = J.stream3;
-  if (!ctx->comb) {  // the -G1 comb (bls_bisect.hip): the MSM pairs' -2^b G1 and the bisection's -r_i G1
+  if (!ctx->comb) {  // the -G1 comb (bls_bisect.hip): the MSM pairs' -w_b G1 and the bisection's -r_i G1
     G1A* tab = nullptr;
     HIPCK(hipMalloc(&tab, neg_g1_comb_entries() * sizeof(G1A)));
     hipError_t e = launch_neg_g1_comb_table(st, tab);
@@ -1355,7 +1357,8 @@ static int fav_prepare(bls_ctx* ctx, const uint32_t* d_idx, const uint64_t* d_of
 //             ACC_SHARED_MIN items) or k_miller_fused<1> over the batch's
 //             r_i apk_i and H_i again (shared-f batches);
 //   f_sig,i = ML(-r_i G1, sigma_i): -r_i G1 from a fixed-base comb (8 mixed
-//             additions, k_neg_rg1), f by k_miller_fused<1>;
+//             additions, k_neg_rg1; its upper four windows hold phi images, so
+//             r_i = a + b lambda as in the batch), f by k_miller_fused<1>;
 // leaf_i = f_H,i f_sig,i, and a 16-ary product tree above the leaves.  A node's
 // check is FE(node) == 1: the product of e(r_i apk_i, H_i) e(-r_i G1, sigma_i)
 // over its items, the random linear combination of their checks.  The first

@@ -6,10 +6,12 @@
 // rest of the chip to the other streams; per item it needs several times less
 // SIMD time than the 64-lane wave-program versions.
 //   k_sig_lane   [|x|] sigma (G2 subgroup check psi(sigma) == -[|x|] sigma) and
-//                r_i apk_i (G1, 64-bit RLC scalar), one scalar bit per step
+//                r_i apk_i (G1; the 64-bit RLC scalar read as a + b lambda, one joint 32-step chain on apk_i and
+//                phi(apk_i), bls_g1_endo.h)
 //   k_g2x_lane   M = [|x|] B on the hash_to_G2 staging slots (cofactor clearing)
 #include "bls_kernels.h"
 #include "bls_fq_g1.h"
+#include "bls_g1_endo.h"
 #include "bls_fq_g2.h"
 #include "bls_lane.h"
 #include "bls_pp_lane.h"
@@ -30,19 +32,13 @@ __global__ void __launch_bounds__(64) k_sig_lane2(size_t B, const int* gstat, in
                                                   const G1P* apk, const G2A* sig, const uint64_t* rsc, G1P* rPj) {
   __shared__ uint32_t lds[84 * 64];
   const unsigned nb = (unsigned)((B + 63) / 64);
-  if (blockIdx.x < nb) {  // r_i apk_i in the redundant digit form (bls_fq_g1.h), canonical output
+  if (blockIdx.x < nb) {  // r_i apk_i = a apk_i + b phi(apk_i) in the redundant digit form, canonical output
     const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (i >= B || !(gstat[i] && dstat[i])) return;
     const G1P a = apk[i];
     const G1Q A{fq_unpack(a.x), fq_unpack(a.y), fq_unpack(a.z)};
     const uint64_t r = rsc[i];
-    G1Q R{fq_zero(), fq_unpack(FP_ONE), fq_zero()};
-    if ((r >> 63) & 1ull) R = A;
-#pragma unroll 1
-    for (int b = 62; b >= 0; --b) {
-      R = g1q_dbl(R);
-      if ((r >> b) & 1ull) R = g1q_add(R, A);
-    }
+    const G1Q R = g1q_mul_endo(A, (uint32_t)r, (uint32_t)(r >> 32));
     rPj[i] = G1P{fq_pack(R.x), fq_pack(R.y), fq_pack(R.z)};
     return;
   }

@@ -13,14 +13,16 @@
 //                   wave per b, 32 lane pairs adding 4 bucket sums each, then a
 //                   5-level LDS tree (a 16-wave wide-arithmetic variant
 //                   measured C2 -4 %: profiles/r04o_usum_ab.txt)
-//   k_msm_upairs    the 64 pairs (-2^b G1, U_b), U_b affine: the Miller loop
-//                   of (-G1, S) with S = sum_b 2^b U_b is, after the final
-//                   exponentiation, the product of e(-2^b G1, U_b) -- so the
+//   k_msm_upairs    the 64 pairs (-w_b G1, U_b), U_b affine, w_b the weight
+//                   of scalar bit b (2^b below 32, 2^(b - 32) lambda above:
+//                   r_i = a + b lambda, bls_g1_endo.h): the Miller loop
+//                   of (-G1, S) with S = sum_b w_b U_b is, after the final
+//                   exponentiation, the product of e(-w_b G1, U_b) -- so the
 //                   U_b join the batch's own pairs (lines + f accumulation)
 //                   and the 63-doubling weighted sum S (round 4:
 //                   k_msm_weighted_wide, one 16-wave workgroup, ~0.7 ms) and
 //                   its one-pair Miller loop (k_miller_wide, ~0.5 ms) leave
-//                   the latency chain.  The -2^b G1 are entries of the
+//                   the latency chain.  The -w_b G1 are entries of the
 //                   bisection's fixed-base comb (bls_bisect.hip).
 // ~8 additions per signature instead of a 64-step double-and-add.  (The
 // previous form ran one lane pair per bucket -- 64 waves, ~40 dependent
@@ -177,8 +179,9 @@ __global__ void __launch_bounds__(64) k_msm_usum(const Fp* csum, Fp* U) {
   if (j == 0) p2_store(U + 6 * b, R, hi);
 }
 
-// lane b < 64: pair (-2^b G1, U_b) at P[b], Q[b], ok[b] = 1 (U_b = the identity: Q[b].inf, a skipped pair).
-// -2^b G1 = comb[256 (b / 8) + 2^(b % 8)] (comb[256 w + d] = d 2^(8 w) (-G1)).
+// lane b < 64: pair (-w_b G1, U_b) at P[b], Q[b], ok[b] = 1 (U_b = the identity: Q[b].inf, a skipped pair), w_b
+// the weight of scalar bit b: 2^b for b < 32, 2^(b - 32) lambda above (r_i = a + b lambda, bls_g1_endo.h).
+// -w_b G1 = comb[256 (b / 8) + 2^(b % 8)] (comb[256 w + d] = d 2^(8 w) (-G1), its phi image for w >= 4).
 __global__ void __launch_bounds__(64) k_msm_upairs(const Fp* U, const G1A* comb, G1A* P, G2A* Q, int* ok) {
   const int b = threadIdx.x;
   const Fp* u = U + 6 * b;
