@@ -158,6 +158,83 @@ def verify_batch(indices: np.ndarray, msgs32, sigs96, ctx=None) -> np.ndarray:
     return out.astype(bool)
 
 
+def group_messages(msgs32) -> tuple[bytes, np.ndarray]:
+    """Deduplicate B 32-byte messages on the host: (table, msg_ids) with the distinct messages in order of first
+    occurrence and msg_ids[b] (uint32) the table entry of message b, so that
+    table[32 * msg_ids[b]: 32 * msg_ids[b] + 32] == msgs32[32 * b: 32 * b + 32]."""
+    raw = _u8(msgs32).tobytes()
+    if len(raw) % 32:
+        raise ValueError("messages must be 32 bytes each")
+    B = len(raw) // 32
+    seen: dict[bytes, int] = {}
+    ids = np.empty(B, dtype=np.uint32)
+    for b in range(B):
+        ids[b] = seen.setdefault(raw[32 * b: 32 * b + 32], len(seen))
+    return b"".join(seen), ids
+
+
+def _shared_args(table, msg_ids, B: int) -> tuple[np.ndarray, int, np.ndarray]:
+    """(table bytes as u8, M, ids as uint32) of a shared-message batch of B items, checked on the host: the ids
+    must name table entries (ValueError otherwise, before any device call)."""
+    t = _u8(table)
+    if t.size % 32:
+        raise ValueError("the message table must be a multiple of 32 bytes")
+    M = t.size // 32
+    raw = np.asarray(msg_ids)
+    if raw.ndim != 1 or raw.size != B:
+        raise ValueError("need one message id per item")
+    if B and raw.dtype.kind not in "ui":
+        raise ValueError("message ids must be integers")
+    if B and M == 0:
+        raise ValueError("an empty message table")
+    if B and (int(raw.min()) < 0 or int(raw.max()) >= M):
+        raise ValueError("message id out of range")
+    return t, M, np.ascontiguousarray(raw, dtype=np.uint32)
+
+
+def fast_aggregate_verify_batch_shared(indices, offsets, table, msg_ids, sigs96, ctx=None) -> np.ndarray:
+    """fast_aggregate_verify_batch for items that share messages: item b signs table[32 * msg_ids[b] ..] (see
+    group_messages).  Same verdicts as the unshared call on the expanded messages, with one hash_to_G2 and one
+    Miller pair per table entry instead of per item (bls_fav_batch_indexed_shared).  Worth it when the table is
+    shorter than the batch."""
+    idx = np.ascontiguousarray(indices, dtype=np.uint32)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    B = offs.size - 1
+    t, M, ids = _shared_args(table, msg_ids, B)
+    s = _u8(sigs96)
+    if s.size != 96 * B:
+        raise ValueError("need one 96-byte signature per aggregate")
+    c = ctx or _native.context()
+    out = np.zeros(B, dtype=np.uint8)
+    c.check(c.lib.bls_fav_batch_indexed_shared(c.h, _ptr(idx), _ptr(offs), B, t.tobytes(), M, _ptr(ids), s.tobytes(),
+                                               _ptr(out)))
+    return out.astype(bool)
+
+
+def verify_batch_shared(indices, table, msg_ids, sigs96, ctx=None) -> np.ndarray:
+    """verify_batch for items that share messages (fast_aggregate_verify_batch_shared with one key per item)."""
+    idx = np.ascontiguousarray(indices, dtype=np.uint32)
+    B = idx.size
+    t, M, ids = _shared_args(table, msg_ids, B)
+    s = _u8(sigs96)
+    if s.size != 96 * B:
+        raise ValueError("need one 96-byte signature per item")
+    c = ctx or _native.context()
+    out = np.zeros(B, dtype=np.uint8)
+    c.check(c.lib.bls_verify_batch_indexed_shared(c.h, _ptr(idx), B, t.tobytes(), M, _ptr(ids), s.tobytes(),
+                                                  _ptr(out)))
+    return out.astype(bool)
+
+
+def batch_work(ctx=None) -> tuple[int, int]:
+    """(messages hashed, Miller pairs) of the last FAV / Verify batch prepared on the context: (B, B + 64)
+    unshared, (M, M + 64) shared."""
+    c = ctx or _native.context()
+    h, p = ctypes.c_uint64(), ctypes.c_uint64()
+    c.check(c.lib.bls_last_batch_work(c.h, ctypes.byref(h), ctypes.byref(p)))
+    return int(h.value), int(p.value)
+
+
 def aggregate_verify_batch(pubkeys, messages, signatures, ctx=None) -> np.ndarray:
     """B AggregateVerify calls -> bool array.  pubkeys[b] / messages[b]: item b's lists of 48-byte keys
     and messages (any lengths, equal list lengths); signatures[b]: 96 bytes.  An item whose lists differ
@@ -322,14 +399,23 @@ class ResidentFavBatch:
     final-exponentiated by ``check_partials``; ``finish()`` writes verdicts.
     """
 
-    def __init__(self, indices, offsets, msgs32, sigs96, ctx=None, chunks: int = 1):
+    def __init__(self, indices, offsets, msgs32, sigs96, ctx=None, chunks: int = 1, msg_ids=None):
         """chunks > 1 splits the batch into that many equal sub-batches (uniform committee size only), each
         submitted as its own FAV job: a pass over the batch is `chunks` jobs (large shards, e.g. the C4 firehose,
-        stay within one job's scratch)."""
-        self.ctx = ctx or _native.context()
+        stay within one job's scratch).
+
+        msg_ids (one per item): the items share messages -- msgs32 is then the message table and item b signs
+        entry msg_ids[b] (group_messages); the batch runs through the job API (run_pipelined / run), one hash and
+        one Miller pair per table entry.  Needs chunks == 1."""
         offs = np.ascontiguousarray(offsets, dtype=np.uint64)
         self.B = int(offs.size - 1)
         self.chunks = max(1, int(chunks))
+        self.msg_ids, self.M = None, 0
+        if msg_ids is not None:
+            if self.chunks != 1:
+                raise ValueError("a shared-message batch needs chunks == 1")
+            _, self.M, self.msg_ids = _shared_args(msgs32, msg_ids, self.B)
+        self.ctx = ctx or _native.context()
         if self.chunks > 1:
             n = int(offs[1] - offs[0]) if self.B else 0
             if self.B % self.chunks or not np.array_equal(offs, np.arange(self.B + 1, dtype=np.uint64) * n):
@@ -348,8 +434,8 @@ class ResidentFavBatch:
         self._chunk_job = [0] * self.chunks  # job whose buffer holds each chunk's latest verdicts
 
     def partial(self, seed32: bytes | None = None) -> bytes:
-        if self.chunks > 1:
-            raise ValueError("a chunked batch runs through the job API (run_pipelined)")
+        if self.chunks > 1 or self.msg_ids is not None:
+            raise ValueError("a chunked or shared-message batch runs through the job API (run_pipelined)")
         seed = seed32 if seed32 is not None else os.urandom(32)
         buf = ctypes.create_string_buffer(576)
         c = self.ctx
@@ -376,6 +462,10 @@ class ResidentFavBatch:
     def submit(self, job: int, seed32: bytes, chunk: int = 0) -> None:
         c = self.ctx
         idx, msgs, sigs, _ = self._chunk_ptrs(chunk)
+        if self.msg_ids is not None:
+            c.check(c.lib.bls_fav_job_submit_shared_dev(c.h, job, idx, self.offs.ptr, self.cb, msgs, self.M,
+                                                        _ptr(self.msg_ids), sigs, seed32))
+            return
         c.check(c.lib.bls_fav_job_submit_dev(c.h, job, idx, self.offs.ptr, self.cb, msgs, sigs, seed32))
 
     def job_partial(self, job: int) -> bytes:
@@ -445,6 +535,9 @@ class ResidentFavBatch:
                               ).astype(bool)
 
     def run(self) -> np.ndarray:
+        if self.msg_ids is not None:
+            self.run_pipelined([os.urandom(32)])
+            return self.verdicts()
         ok = self.check_partials(self.partial())
         self.finish(ok)
         return self.verdicts()

@@ -168,9 +168,14 @@ def _b(x) -> bytes:
 class SignatureSets:
     """Collects verify calls; ``verify()`` checks them in as few device batches as possible."""
 
-    def __init__(self, registry: _batch.Registry | None = None, ctx=None):
+    def __init__(self, registry: _batch.Registry | None = None, ctx=None, share_messages: bool = False):
+        """share_messages: when the indexed sets hold fewer distinct messages than sets (the attestations of a
+        slot, the aggregates of a committee, sync-committee messages), check them through
+        ``batch.fast_aggregate_verify_batch_shared``: one hash_to_G2 and one Miller pair per distinct message.
+        Same verdicts; off by default."""
         self.registry = registry
         self.ctx = ctx
+        self.share_messages = share_messages
         self.sets: list[_Set] = []
         self.eager = 0  # verify calls inside deferred() that ran at once (result not asserted)
 
@@ -264,7 +269,11 @@ class SignatureSets:
             offs = _batch.offsets_from_lengths([x.size for _, x in indexed])
             msgs = b"".join(self.sets[i].messages[0] for i in ids)
             sigs = b"".join(self.sets[i].signature for i in ids)
-            v = _batch.fast_aggregate_verify_batch(idx, offs, msgs, sigs, ctx=self.ctx)
+            table, mids = _batch.group_messages(msgs) if self.share_messages else (msgs, None)
+            if mids is not None and len(table) < len(msgs):
+                v = _batch.fast_aggregate_verify_batch_shared(idx, offs, table, mids, sigs, ctx=self.ctx)
+            else:
+                v = _batch.fast_aggregate_verify_batch(idx, offs, msgs, sigs, ctx=self.ctx)
             for i, ok in zip(ids, v):
                 out[i] = bool(ok)
         if av:
@@ -289,15 +298,15 @@ class SignatureSets:
 
 
 @contextlib.contextmanager
-def deferred(registry: _batch.Registry | None = None, ctx=None, check: bool = True):
+def deferred(registry: _batch.Registry | None = None, ctx=None, check: bool = True, share_messages: bool = False):
     """Within the block, ``bls_mi355x.bls.Verify/FastAggregateVerify/AggregateVerify`` calls whose result is
     asserted record their arguments into a ``SignatureSets`` and return True (every other call runs at once,
     see the module docstring); at exit the sets are verified in batches and, with ``check``, an
     AssertionError names the first invalid one.  Yields the collector (its ``results`` attribute holds the
-    verdicts after the block)."""
+    verdicts after the block).  share_messages: see ``SignatureSets``."""
     from . import bls as shim
 
-    sets = SignatureSets(registry, ctx)
+    sets = SignatureSets(registry, ctx, share_messages)
     prev = shim._collector
     shim._collector = sets
     try:

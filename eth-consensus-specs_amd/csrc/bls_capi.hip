@@ -13,6 +13,8 @@
 
 #include "../../include/blsmi355x.h"
 #include "bls_kernels.h"
+#define BLS_SEGSUM_PLAN_ONLY  // the host plan of the segmented G1 sum; its kernels are in bls_segsum.hip
+#include "bls_g1_segsum.h"
 
 using namespace bls;
 
@@ -40,6 +42,10 @@ enum Slot {
   S_OWN,  // the job's own final check (job_submit)
   S_GAFF, S_GREDO,  // the affine gather's level lists and redo flags (bls_gather_aff.hip)
   S_COMM, S_CV,  // the all-gathered partials of all ranks and their check's verdict (enqueue_comm_check)
+  // shared-message batches (fav_prepare with a grouping): the pair arrays' status and G1 side (M + MSM_UPAIRS; the
+  // G2 side is S_H), the group sums before the affine conversion, the fold's two partial arrays, its runs and sorted
+  // item list, the items' message ids, and the bisection's per-item H
+  S_PSTAT, S_GP, S_GSUM, S_SEGA, S_SEGB, S_SEGRUN, S_SEGIT, S_MSGID, S_BHIT,
   NSLOT
 };
 
@@ -84,6 +90,11 @@ struct Job {
   bool comm_pending = false;
   hipEvent_t ev_comm = nullptr, ev_cv = nullptr;
   int fav_mg = 1;  // pairs per f of the prepared batch's Miller accumulation
+  // the prepared batch shares messages (fav_prepare with a grouping): its pair arrays are per message, and the
+  // bisection takes its per-item H through S_MSGID; seg / seg_ids: the host plan and ids its uploads read
+  bool fav_shared = false;
+  SegPlan seg;
+  std::vector<uint32_t> seg_ids;
   // last bisection fallback: final-exponentiation checks and rounds (levels); the checks of a FAV bisection are
   // counted on the device (bis_dev_checks, read after the job's stream by bls_last_fallback_stats)
   uint64_t bis_checks = 0, bis_rounds = 0;
@@ -99,6 +110,7 @@ struct bls_ctx {
   std::string err;
   G1A* comb = nullptr;  // -G1 comb of the bisection fallback (bls_bisect.hip), built on first use
   Job* stats_job = &jobs[0];  // the job whose fallback statistics bls_last_fallback_stats reports
+  uint64_t last_hashes = 0, last_pairs = 0;  // work of the last prepared FAV batch (bls_last_batch_work)
   // Context-wide streams for the kernels with large private segments (the h2c
   // fallback, 6,000 B/lane; final-exponentiation checks, 3,296 B/lane): the
   // runtime gives every hardware queue that runs such a kernel a scratch
@@ -1192,16 +1204,32 @@ static bool miller_fused() {
 constexpr size_t ACC8_MAX = 2048;  // items per FAV batch below which one pair per f runs on eight lanes
 constexpr size_t ACC_SHARED_MIN = 4096;  // items per FAV batch from which k_miller_acc4q shares f between two pairs
 
+// msg_id (host, B entries, nullable) / M: a shared-message batch -- d_msgs is a table of M messages and item i signs
+// entry msg_id[i].  The per-item stages (gather, decode, r_i apk_i chains, MSM) run over the B items as ever; the
+// per-message stages (hash_to_G2, G2 lines, f accumulation) run over M + MSM_UPAIRS pairs whose G1 side is the
+// segmented sum of the items' r_i apk_i (bls_g1_segsum.h), and the kernel-form thresholds key on M.  Without a
+// grouping (every existing entry point) the launches are what they always were.
 static int fav_prepare(bls_ctx* ctx, const uint32_t* d_idx, const uint64_t* d_offs, size_t B, const uint8_t* d_msgs,
-                       const uint8_t* d_sigs, const uint8_t* seed32, Fp12** out_f) {
+                       const uint8_t* d_sigs, const uint8_t* seed32, Fp12** out_f, size_t M = 0,
+                       const uint32_t* msg_id = nullptr) {
   if (!ctx->reg || !ctx->reg_n) {
     ctx->err = "no registry loaded";
     return BLS_E_NOREG;
   }
+  const bool shared = msg_id != nullptr;
+  if (shared) {  // the plan first: a bad id is refused before any device call
+    Job& Jp = *ctx->j;
+    if (!seg_plan(msg_id, B, M, Jp.seg)) {
+      ctx->err = "msg_id out of range (or an empty message table)";
+      return BLS_E_ARG;
+    }
+    Jp.seg_ids.assign(msg_id, msg_id + B);
+  }
+  const size_t NH = shared ? M : B;  // messages hashed = pairs of the H side
   // pairs 0 .. B: (r_i apk_i, H_i); pairs B .. B + 64: (-w_b G1, U_b), the MSM's bit-sums (bls_msm.hip).  The 64
   // scalar bits read as r_i = a + b lambda (a the low, b the high half; lambda = -x^2 mod r, phi's eigenvalue on
   // G1): bit b weighs w_b = 2^b below 32 and 2^(b - 32) lambda above, on both sides (bls_g1_endo.h, the comb)
-  const size_t NP = B + MSM_UPAIRS;
+  const size_t NP = NH + MSM_UPAIRS;
   int *status, *gstat, *flag, *dstat;
   G1P *apka, *rpj;
   G1A* rP;
@@ -1211,18 +1239,36 @@ static int fav_prepare(bls_ctx* ctx, const uint32_t* d_idx, const uint64_t* d_of
   uint64_t* rsc;
   uint32_t* msmu;
   uint8_t* d_seed;
-  SCR(S_STATUS, NP, status);
+  SCR(S_STATUS, shared ? B : NP, status);
   SCR(S_GSTAT, B, gstat);
   SCR(S_APKA, B, apka);
   SCR(S_SIG, B, sig);
-  SCR(S_RP, NP, rP);
+  SCR(S_RP, shared ? B : NP, rP);
   SCR(S_H, NP, H);
-  SCR(S_FLAG, B, flag);
+  SCR(S_FLAG, NH, flag);
   SCR(S_RSC, B, rsc);
   SCR(S_MSMU, msm_scratch_u32(B), msmu);
   SCR(S_MSMF, msm_scratch_fd(), msmf);
-  SCR(S_HCF, h2c_scratch_fd(B), hcf);
+  SCR(S_HCF, h2c_scratch_fd(NH), hcf);
   SCR(S_RPJ, B, rpj);
+  // the Miller pairs' status and G1 side: the item arrays themselves, [0, B) items then the MSM pairs -- or, shared,
+  // arrays of their own, [0, M) group sums then the MSM pairs, beside item arrays of B
+  int* pstat = status;
+  G1A* pP = rP;
+  G1P *gsum = nullptr, *sega = nullptr, *segb = nullptr;
+  SegRun* d_runs = nullptr;
+  uint32_t *d_items = nullptr, *d_msgid = nullptr;
+  if (shared) {
+    const SegPlan& sp = ctx->j->seg;
+    SCR(S_PSTAT, NP, pstat);
+    SCR(S_GP, NP, pP);
+    SCR(S_GSUM, M, gsum);
+    SCR(S_SEGA, sp.max_tmp(), sega);
+    SCR(S_SEGB, sp.levels() > 1 ? sp.level_tmp[1] : 0, segb);
+    SCR(S_SEGRUN, sp.runs.size(), d_runs);
+    SCR(S_SEGIT, B, d_items);
+    SCR(S_MSGID, B, d_msgid);
+  }
   // Miller loop of all NP pairs, split: G2 lines (k_miller_lines2) on stream2 after hash_to_G2 and the MSM, f
   // accumulated on stream1 by k_miller_acc4q (four lanes per f, G pairs per f: one squaring per step for all G)
   uint32_t* mlines = nullptr;
@@ -1257,6 +1303,16 @@ static int fav_prepare(bls_ctx* ctx, const uint32_t* d_idx, const uint64_t* d_of
   // the branches fork from stream1's tail -- or, after a bisection still running there, from the point where it
   // has copied everything it reads of the state stream2 / stream3 write (fav_bisect); the seed goes on the
   // decode's stream, its reader, so the fork need not follow stream1
+  if (shared) {
+    // the grouping's tables on stream1, behind anything (a bisection's per-item H gather) that still reads the
+    // previous ids; the branches then fork from here, not from a bisection's ev_bis
+    const SegPlan& sp = J.seg;
+    HIPCK(hipMemcpyAsync(d_msgid, J.seg_ids.data(), B * 4, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(d_items, sp.grp_items.data(), B * 4, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(d_runs, sp.runs.data(), sp.runs.size() * sizeof(SegRun), hipMemcpyHostToDevice, st));
+    J.bis_pending = false;
+  }
+  J.fav_shared = shared;
   HIPCK(hipMemcpyAsync(d_seed, seed32, 32, hipMemcpyHostToDevice, sd));
   // Branches, three streams:
   //   stream1: registry gather (affine apk) -> subgroup / r_i apk_i chains -> f accumulation
@@ -1272,9 +1328,12 @@ static int fav_prepare(bls_ctx* ctx, const uint32_t* d_idx, const uint64_t* d_of
   }
   HIPCK(hipStreamWaitEvent(st2, fork, 0));
   if (!two) HIPCK(hipStreamWaitEvent(st3, fork, 0));
-  PROF2(2, st2, launch_h2c(st2, B, d_msgs, nullptr, hcf, H, flag));
-  CK(h2c_fallback(ctx, st2, B, d_msgs, nullptr, flag, H));
-  PROF2(1, sd, launch_sig_decode(sd, B, d_msgs, d_sigs, d_seed, sig, rsc, dstat));
+  PROF2(2, st2, launch_h2c(st2, NH, d_msgs, nullptr, hcf, H, flag));
+  CK(h2c_fallback(ctx, st2, NH, d_msgs, nullptr, flag, H));
+  if (shared)
+    PROF2(1, sd, launch_sig_decode_idx(sd, B, d_msgs, d_msgid, d_sigs, d_seed, sig, rsc, dstat));
+  else
+    PROF2(1, sd, launch_sig_decode(sd, B, d_msgs, d_sigs, d_seed, sig, rsc, dstat));
   HIPCK(hipEventRecord(J.ev_sig, sd));
   // the registry gather: the complete-formula kernel (k_fav_gather_q, 108 registers: four waves per SIMD, beside the
   // one-wave lane kernels whose register files it fits into), or with BLS_GATHER=affine (read per batch) affine
@@ -1302,7 +1361,7 @@ static int fav_prepare(bls_ctx* ctx, const uint32_t* d_idx, const uint64_t* d_of
   // stream1 while (or after) the MSM runs.
   hipStream_t sm = two ? st : st3;
   if (!two) HIPCK(hipStreamWaitEvent(sm, J.ev_gather, 0));
-  PROF2(11, sm, launch_msm_upairs(sm, B, gstat, dstat, rsc, sig, msmu, msmf, ctx->comb, rP + B, H + B, status + B));
+  PROF2(11, sm, launch_msm_upairs(sm, B, gstat, dstat, rsc, sig, msmu, msmf, ctx->comb, pP + NH, H + NH, pstat + NH));
   HIPCK(hipEventRecord(J.ev_msm, sm));
   // the Miller loops of all NP pairs: the G2 lines on stream2 after the hash and the MSM, then the f accumulation on
   // stream1 -- or (BLS_MILLER_FUSED=1) one fused kernel (k_miller_fused, lines in LDS) on stream1
@@ -1314,6 +1373,18 @@ static int fav_prepare(bls_ctx* ctx, const uint32_t* d_idx, const uint64_t* d_of
   HIPCK(hipEventRecord(J.ev_join, st2));
   if (!two) HIPCK(hipStreamWaitEvent(st, J.ev_sig, 0));
   PROF(10, launch_sig_vm(st, B, gstat, status, dstat, apka, sig, rsc, rpj, rP));
+  if (shared) {
+    // the segmented sum of the items' affine r_i apk_i into one point per message: a launch per fold level, the
+    // partial arrays alternating, then the M sums to affine (ok 0 -- an empty, rejected or cancelling group --
+    // gives .inf, a dead pair whose factor is 1)
+    const SegPlan& sp = J.seg;
+    for (size_t l = 0; l < sp.levels(); ++l) {
+      const uint32_t n = sp.level_off[l + 1] - sp.level_off[l];
+      G1P *in = (l & 1) ? sega : segb, *out = (l & 1) ? segb : sega;
+      LK(launch_g1_seg_fold(st, (int)l, d_runs + sp.level_off[l], n, d_items, status, rP, in, out, gsum, pstat));
+    }
+    LK(launch_g1_affine(st, M, pstat, gsum, pP));
+  }
   HIPCK(hipStreamWaitEvent(st, J.ev_join, 0));
   if (fused && !two) HIPCK(hipStreamWaitEvent(st, J.ev_msm, 0));
   // four pairs share each f (one squaring per step for all four) on full batches: the least work per pair, and
@@ -1324,7 +1395,7 @@ static int fav_prepare(bls_ctx* ctx, const uint32_t* d_idx, const uint64_t* d_of
   static const int acc_g = getenv("BLS_ACC_G") ? atoi(getenv("BLS_ACC_G")) : 4;  // pairs per f of full batches
   static const size_t shared_min = getenv("BLS_ACC_SHARED_MIN") ? (size_t)atol(getenv("BLS_ACC_SHARED_MIN"))
                                                                 : ACC_SHARED_MIN;
-  const int mg = B >= shared_min ? (acc_g == 8 || acc_g == 4 || acc_g == 1 ? acc_g : 2) : 1;
+  const int mg = NH >= shared_min ? (acc_g == 8 || acc_g == 4 || acc_g == 1 ? acc_g : 2) : 1;
   J.fav_mg = mg;
   // knob BLS_ACC_LL = 1: G = 4 with each step's four lines multiplied together before they meet f
   // (k_miller_acc4l: 12 Fp2 products per lane per round of four lines instead of 16, but the Karatsuba sums'
@@ -1336,14 +1407,16 @@ static int fav_prepare(bls_ctx* ctx, const uint32_t* d_idx, const uint64_t* d_of
   // the SIMD time does (C3's 2,048: -8.6 %; profiles/r06y_acc8_ab.txt).  Knob BLS_ACC8_MAX.
   static const size_t acc8_max = getenv("BLS_ACC8_MAX") ? (size_t)atol(getenv("BLS_ACC8_MAX")) : ACC8_MAX;
   if (fused)
-    PROF(5, launch_miller_fused(st, rP, H, status, NP, f, mg));
-  else if (mg == 1 && B < acc8_max)
-    PROF(5, launch_miller_acc8(st, rP, H, status, NP, mlines, miller_lines_ld(NP), f));
+    PROF(5, launch_miller_fused(st, pP, H, pstat, NP, f, mg));
+  else if (mg == 1 && NH < acc8_max)
+    PROF(5, launch_miller_acc8(st, pP, H, pstat, NP, mlines, miller_lines_ld(NP), f));
   else if (mg == 4 && acc_ll)
-    PROF(5, launch_miller_acc4l(st, rP, H, status, NP, mlines, miller_lines_ld(NP), f));
+    PROF(5, launch_miller_acc4l(st, pP, H, pstat, NP, mlines, miller_lines_ld(NP), f));
   else
-    PROF(5, launch_miller_acc4(st, rP, H, status, NP, mlines, miller_lines_ld(NP), f, mg));
+    PROF(5, launch_miller_acc4(st, pP, H, pstat, NP, mlines, miller_lines_ld(NP), f, mg));
   PROF(6, launch_fp12_prod_vm(st, f, (NP + mg - 1) / mg, ft, fo));
+  ctx->last_hashes = NH;
+  ctx->last_pairs = NP;
   J.fav_B = B;
   J.fav_ready = true;
   *out_f = fo;
@@ -1376,7 +1449,7 @@ static int fav_bisect(bls_ctx* ctx, bool root_bad, uint8_t* d_out) {
   const int* status = (const int*)J.buf[S_STATUS].p;
   const uint64_t* rsc0 = (const uint64_t*)J.buf[S_RSC].p;
   const G1A* rP = (const G1A*)J.buf[S_RP].p;
-  const G2A* H = (const G2A*)J.buf[S_H].p;
+  const G2A* H = (const G2A*)J.buf[S_H].p;  // per item; per message for a shared-message batch (H_item below)
   const G2A* sig0 = (const G2A*)J.buf[S_SIG].p;
   Fp12* fb = (Fp12*)J.buf[S_FAV_F].p;
   std::vector<size_t> off{0}, cnt{B};
@@ -1405,12 +1478,21 @@ static int fav_bisect(bls_ctx* ctx, bool root_bad, uint8_t* d_out) {
   SCR(S_BSIG, B, sig);
   SCR(S_BRSC, B, rsc);
 
-  if (J.fav_mg > 1) SCR(S_BSEL, B, fH);
+  // per-item f_H: the batch's own f (one pair per f), else recomputed -- always for a shared-message batch, whose
+  // pairs are per message: over the items' r_i apk_i and H_item[i] = H[msg_id[i]]
+  const bool refH = J.fav_mg > 1 || J.fav_shared;
+  G2A* Hit = nullptr;
+  if (J.fav_shared) SCR(S_BHIT, B, Hit);
+  if (refH) SCR(S_BSEL, B, fH);
   else fH = fb;
   hipStream_t st = J.stream;
   // first everything read of the state that the job's next batch writes from stream2 / stream3 (H and the line
   // records, sigma_i, r_i); that batch forks from ev_bis (fav_prepare) while the rest runs here
-  if (J.fav_mg > 1) LK(launch_miller_fused(st, rP, H, status, B, fH, 1));
+  if (J.fav_shared) {
+    LK(launch_g2a_gather(st, B, H, (const uint32_t*)J.buf[S_MSGID].p, Hit));
+    H = Hit;
+  }
+  if (refH) LK(launch_miller_fused(st, rP, H, status, B, fH, 1));
   HIPCK(hipMemcpyAsync(sig, sig0, B * sizeof(G2A), hipMemcpyDeviceToDevice, st));
   HIPCK(hipMemcpyAsync(rsc, rsc0, B * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
   HIPCK(hipEventRecord(J.ev_bis, st));
@@ -1496,8 +1578,15 @@ static int host_seed(bls_ctx* ctx, uint8_t seed[32]) {
 }
 
 // One host-buffer FAV batch: copies in, RLC batch check, bisection on failure.
+// msg_id (nullable) / M: msgs32 is a table of M messages and item b signs entry msg_id[b] (fav_prepare)
 static int fav_batch_host(bls_ctx* ctx, const uint32_t* idx, const uint64_t* offsets, size_t B, const uint8_t* msgs32,
-                          const uint8_t* sigs96, uint8_t* out) {
+                          const uint8_t* sigs96, uint8_t* out, size_t M = 0, const uint32_t* msg_id = nullptr) {
+  if (msg_id) {  // before any device call
+    if (!M) return BLS_E_ARG;
+    for (size_t b = 0; b < B; b++)
+      if (msg_id[b] >= M) return BLS_E_ARG;
+  }
+  const size_t nmsg = msg_id ? M : B;
   const uint64_t nidx = offsets[B];
   if (nidx && !idx) return BLS_E_ARG;
   if (nidx > 0xffffffffull * 64) return BLS_E_ARG;
@@ -1508,12 +1597,12 @@ static int fav_batch_host(bls_ctx* ctx, const uint32_t* idx, const uint64_t* off
   uint8_t *d_m, *d_s, *d_out;
   SCR(S_IN0, nidx, d_idx);
   SCR(S_OFFS, B + 1, d_offs);
-  SCR(S_IN1, 32 * B, d_m);
+  SCR(S_IN1, 32 * nmsg, d_m);
   SCR(S_IN2, 96 * B, d_s);
   SCR(S_IN3, B, d_out);
   CK(h2d(ctx, d_idx, idx, nidx * 4));
   CK(h2d(ctx, d_offs, offsets, (B + 1) * 8));
-  CK(h2d(ctx, d_m, msgs32, 32 * B));
+  CK(h2d(ctx, d_m, msgs32, 32 * nmsg));
   CK(h2d(ctx, d_s, sigs96, 96 * B));
   uint8_t seed[32];
   CK(host_seed(ctx, seed));
@@ -1521,7 +1610,7 @@ static int fav_batch_host(bls_ctx* ctx, const uint32_t* idx, const uint64_t* off
   // (an earlier call's, recorded before these copies; the hash would read the previous contents of S_IN1)
   ctx->j->bis_pending = false;
   Fp12* f;
-  CK(fav_prepare(ctx, d_idx, d_offs, B, d_m, d_s, seed, &f));
+  CK(fav_prepare(ctx, d_idx, d_offs, B, d_m, d_s, seed, &f, M, msg_id));
   int ok = run_final_check(ctx, f);
   if (ok < 0) return ok;
   CK(fav_finish(ctx, ok, true, d_out));
@@ -1548,6 +1637,32 @@ int bls_verify_batch_indexed(bls_ctx* ctx, const uint32_t* idx, size_t B, const 
   std::vector<uint64_t> offs(B + 1);
   for (size_t i = 0; i <= B; i++) offs[i] = i;
   return fav_batch_host(ctx, idx, offs.data(), B, msgs32, sigs96, out);
+}
+
+int bls_fav_batch_indexed_shared(bls_ctx* ctx, const uint32_t* idx, const uint64_t* offsets, size_t B,
+                                 const uint8_t* msgs32, size_t M, const uint32_t* msg_id, const uint8_t* sigs96,
+                                 uint8_t* out) {
+  API_ENTER(ctx);
+  if ((!offsets || !msgs32 || !msg_id || !sigs96 || !out) && B) return BLS_E_ARG;
+  if (!B) return 1;
+  return fav_batch_host(ctx, idx, offsets, B, msgs32, sigs96, out, M, msg_id);
+}
+
+int bls_verify_batch_indexed_shared(bls_ctx* ctx, const uint32_t* idx, size_t B, const uint8_t* msgs32, size_t M,
+                                    const uint32_t* msg_id, const uint8_t* sigs96, uint8_t* out) {
+  API_ENTER(ctx);
+  if ((!idx || !msgs32 || !msg_id || !sigs96 || !out) && B) return BLS_E_ARG;
+  if (!B) return 1;
+  std::vector<uint64_t> offs(B + 1);
+  for (size_t i = 0; i <= B; i++) offs[i] = i;
+  return fav_batch_host(ctx, idx, offs.data(), B, msgs32, sigs96, out, M, msg_id);
+}
+
+int bls_last_batch_work(bls_ctx* ctx, uint64_t* hashes, uint64_t* miller_pairs) {
+  API_ENTER(ctx);
+  if (hashes) *hashes = ctx->last_hashes;
+  if (miller_pairs) *miller_pairs = ctx->last_pairs;
+  return 0;
 }
 
 int bls_aggregate_verify_batch(bls_ctx* ctx, const uint8_t* pks48, const uint8_t* msgs, const uint64_t* msg_offs,
@@ -2058,13 +2173,14 @@ static int enqueue_comm_check(bls_ctx* ctx) {
 // product.  B == 0 (a rank whose shard is empty) is allowed only with the exchange: its partial is the identity, so
 // the rank still joins every all-gather and its peers never wait for it.
 static int job_submit(bls_ctx* ctx, const uint32_t* d_idx, const uint64_t* d_offsets, size_t B, const uint8_t* d_msgs32,
-                      const uint8_t* d_sigs96, const uint8_t* seed32, bool exchange) {
+                      const uint8_t* d_sigs96, const uint8_t* seed32, bool exchange, size_t M = 0,
+                      const uint32_t* msg_id = nullptr) {
   exchange = exchange && ctx->comm;
   if (!seed32 || (B && (!d_offsets || !d_msgs32 || !d_sigs96)) || (!B && !exchange)) return BLS_E_ARG;
   Job& J = *ctx->j;
   Fp12* f;
   if (B) {
-    CK(fav_prepare(ctx, d_idx, d_offsets, B, d_msgs32, d_sigs96, seed32, &f));
+    CK(fav_prepare(ctx, d_idx, d_offsets, B, d_msgs32, d_sigs96, seed32, &f, M, msg_id));
   } else {
     SCR(S_FPART, 1, f);
     hipLaunchKernelGGL(k_fp12_set_one, dim3(1), dim3(64), 0, J.stream, f);
@@ -2205,6 +2321,17 @@ int bls_fav_job_submit_dev(bls_ctx* ctx, int job, const uint32_t* d_idx, const u
   const int r = job_submit(ctx, d_idx, d_offsets, B, d_msgs32, d_sigs96, seed32, true);
   // with a communicator, a rank that fails here never enqueues the all-gather its peers are (or will be) in:
   // abort, so their collectives fail instead of hanging (comm_fail_abort)
+  if (r < 0 && ctx->comm) comm_fail_abort(ctx);
+  return r;
+}
+
+int bls_fav_job_submit_shared_dev(bls_ctx* ctx, int job, const uint32_t* d_idx, const uint64_t* d_offsets, size_t B,
+                                  const uint8_t* d_msgs32, size_t M, const uint32_t* msg_id,
+                                  const uint8_t* d_sigs96, const uint8_t* seed32) {
+  JOB_ENTER(ctx, job);
+  int r = BLS_E_ARG;
+  if (!B || msg_id)  // an empty shard has no ids; fav_prepare refuses M == 0 and ids >= M before any device call
+    r = job_submit(ctx, d_idx, d_offsets, B, d_msgs32, d_sigs96, seed32, true, M, B ? msg_id : nullptr);
   if (r < 0 && ctx->comm) comm_fail_abort(ctx);
   return r;
 }

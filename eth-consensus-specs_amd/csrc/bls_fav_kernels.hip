@@ -91,12 +91,15 @@ static __device__ uint64_t rlc_scalar_fav(const uint8_t* seed32, uint64_t i, con
 // RLC scalar.  Independent of the registry gather, so it runs beside it.
 // The identity signature can only verify against the identity key, which the
 // gather rejects: it is marked invalid here.
-__global__ void __launch_bounds__(64) k_sig_decode(size_t B, const uint8_t* msgs32, const uint8_t* sigs96,
-                                                   const uint8_t* seed32, G2A* sig, uint64_t* rsc, int* dstat) {
+// IDX: item i's message is msgs32 + 32 msg_id[i] (a shared-message batch's table), else msgs32 + 32 i.
+template <bool IDX>
+__global__ void __launch_bounds__(64) k_sig_decode(size_t B, const uint8_t* msgs32, const uint32_t* msg_id,
+                                                   const uint8_t* sigs96, const uint8_t* seed32, G2A* sig,
+                                                   uint64_t* rsc, int* dstat) {
   const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (i >= B) return;
   // the hash first: nothing of the decompression is live across its three compressions
-  const uint64_t r = rlc_scalar_fav(seed32, i, msgs32 + 32 * i, sigs96 + 96 * i);
+  const uint64_t r = rlc_scalar_fav(seed32, i, msgs32 + 32 * (IDX ? (size_t)msg_id[i] : i), sigs96 + 96 * i);
   G2A q{fp2_zero(), fp2_zero(), true};
   const int st = g2_decompress_lane_w(q, sigs96 + 96 * i) == DEC_OK ? 1 : 0;
   rsc[i] = st ? r : 0;
@@ -464,7 +467,16 @@ hipError_t launch_h2c_fallback(hipStream_t st, size_t B, const uint8_t* msgs, co
 hipError_t launch_sig_decode(hipStream_t st, size_t B, const uint8_t* msgs32, const uint8_t* sigs96,
                              const uint8_t* seed32, G2A* sig, uint64_t* rsc, int* dstat) {
   if (!B) return hipSuccess;
-  hipLaunchKernelGGL(k_sig_decode, dim3(nblk(B, 64)), dim3(64), 0, st, B, msgs32, sigs96, seed32, sig, rsc, dstat);
+  hipLaunchKernelGGL(k_sig_decode<false>, dim3(nblk(B, 64)), dim3(64), 0, st, B, msgs32, (const uint32_t*)nullptr,
+                     sigs96, seed32, sig, rsc, dstat);
+  return hipGetLastError();
+}
+
+hipError_t launch_sig_decode_idx(hipStream_t st, size_t B, const uint8_t* msgs32, const uint32_t* msg_id,
+                                 const uint8_t* sigs96, const uint8_t* seed32, G2A* sig, uint64_t* rsc, int* dstat) {
+  if (!B) return hipSuccess;
+  hipLaunchKernelGGL(k_sig_decode<true>, dim3(nblk(B, 64)), dim3(64), 0, st, B, msgs32, msg_id, sigs96, seed32, sig,
+                     rsc, dstat);
   return hipGetLastError();
 }
 

@@ -59,6 +59,10 @@ hipError_t launch_h2c_msgs(hipStream_t st, size_t B, const uint8_t* msgs, const 
 hipError_t launch_h2c_fallback(hipStream_t st, size_t B, const uint8_t* msgs, const uint64_t* offs, const int* flag,
                                G2A* H);
 hipError_t launch_sig_decode(hipStream_t st, size_t B, const uint8_t* msgs32, const uint8_t* sigs96, const uint8_t* seed32, G2A* sig, uint64_t* rsc, int* dstat);
+// the same with item i's message at msgs32 + 32 msg_id[i] (a shared-message batch: r_i still hashes the item's own
+// number, message and signature)
+hipError_t launch_sig_decode_idx(hipStream_t st, size_t B, const uint8_t* msgs32, const uint32_t* msg_id,
+                                 const uint8_t* sigs96, const uint8_t* seed32, G2A* sig, uint64_t* rsc, int* dstat);
 // rPj: B projective scratch points (r_i apk_i before the affine conversion)
 hipError_t launch_sig_vm(hipStream_t st, size_t B, const int* gstat, int* status, const int* dstat, const G1P* apk_aff,
                          const G2A* sig, const uint64_t* rsc, G1P* rPj, G1A* rP);
@@ -112,6 +116,13 @@ hipError_t launch_neg_rg1(hipStream_t st, size_t B, const int* status, const uin
 hipError_t launch_verdicts_res(hipStream_t st, const int* status, const int* res, size_t B, uint8_t* out);
 // projective -> affine with one inversion per 8 items (k_g1_affine_b); status-0 items -> identity
 hipError_t launch_g1_affine(hipStream_t st, size_t B, const int* status, const G1P* Pj, G1A* out);
+// shared-message batches (bls_segsum.hip): one level of the segmented G1 sum (bls_g1_segsum.h; level 0 reads the
+// items' affine rP through `items`, the levels above the partials `prev` of the level below; non-final runs write
+// `tmp`, final runs gsum[group] and ok[group] = sum != identity), and the bisection's H_item[i] = H[msg_id[i]]
+struct SegRun;
+hipError_t launch_g1_seg_fold(hipStream_t st, int level, const SegRun* runs, uint32_t nruns, const uint32_t* items,
+                              const int* status, const G1A* rP, const G1P* prev, G1P* tmp, G1P* gsum, int* ok);
+hipError_t launch_g2a_gather(hipStream_t st, size_t B, const G2A* H, const uint32_t* msg_id, G2A* out);
 // nsel independent checks: out[b] = (FE(f[sel[b]]) == 1)
 hipError_t launch_final_check_sel(hipStream_t st, const Fp12* f, const uint32_t* sel, size_t nsel, int* out);
 hipError_t launch_fp12_chunk_prod(hipStream_t st, const Fp12* in, size_t n, int chunk, Fp12* out);
