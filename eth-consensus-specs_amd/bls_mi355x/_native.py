@@ -57,6 +57,8 @@ _SIGS = {
     "bls_fast_aggregate_verify": (_ip, [_vp, _u8p, _sz, _u8p, _sz, _u8p]),
     "bls_aggregate_verify": (_ip, [_vp, _u8p, _sz, _u8p, ctypes.POINTER(_sz), _u8p]),
     "bls_aggregate": (_ip, [_vp, _u8p, _sz, _vp]),
+    "bls_aggregate_grouped": (_ip, [_vp, _vp, _sz, _vp, _sz, _vp, _ip, _vp, _vp]),
+    "bls_aggregate_grouped_dev": (_ip, [_vp, _vp, _sz, _vp, _sz, _vp, _ip, _vp, _vp]),
     "bls_aggregate_pks": (_ip, [_vp, _u8p, _sz, _vp]),
     "bls_key_validate": (_ip, [_vp, _u8p]),
     "bls_sign": (_ip, [_vp, _u8p, _u8p, _sz, _vp]),

@@ -226,6 +226,58 @@ def verify_batch_shared(indices, table, msg_ids, sigs96, ctx=None) -> np.ndarray
     return out.astype(bool)
 
 
+def _group_args(group_ids, n_groups, include, B: int) -> tuple[np.ndarray, int, np.ndarray | None]:
+    """(ids as uint32, G, mask as u8 or None) of a grouped aggregation of B signatures, checked on the host
+    (ValueError before any device call): one integer id in [0, G) per signature, one mask byte per signature."""
+    raw = np.asarray(group_ids)
+    if raw.ndim != 1 or raw.size != B:
+        raise ValueError("need one group id per signature")
+    if B and raw.dtype.kind not in "ui":
+        raise ValueError("group ids must be integers")
+    if B and int(raw.min()) < 0:
+        raise ValueError("group id out of range")
+    if n_groups is None:
+        G = int(raw.max()) + 1 if B else 0
+    else:
+        G = int(n_groups)
+        if G < 0 or G != n_groups:
+            raise ValueError("n_groups must be a non-negative integer")
+    if B and int(raw.max()) >= G:
+        raise ValueError("group id out of range")
+    mask = None
+    if include is not None:
+        mask = np.asarray(include)
+        if mask.ndim != 1 or mask.size != B:
+            raise ValueError("need one mask entry per signature")
+        mask = np.ascontiguousarray(mask != 0, dtype=np.uint8)
+    return np.ascontiguousarray(raw, dtype=np.uint32), G, mask
+
+
+def _grouped_result(out: np.ndarray, ok: np.ndarray) -> list:
+    raw = out.tobytes()
+    return [raw[96 * g: 96 * g + 96] if ok[g] else None for g in range(ok.size)]
+
+
+def aggregate_grouped(sigs96, group_ids, n_groups=None, include=None, subgroup_check: bool = True, ctx=None) -> list:
+    """n_groups Aggregate calls in one (bls_aggregate_grouped): result[g] is the aggregate of the signatures b with
+    group_ids[b] == g (and include[b] true, when a mask is given), or None where bls.Aggregate would raise -- a
+    group with no included signature, or one whose included signatures do not all decode (and, with
+    subgroup_check, lie in G2).  A bad signature spoils only its own group; an excluded one is never judged.
+    n_groups defaults to max(id) + 1.  subgroup_check=False is for signatures a batch has already verified
+    (include = its verdicts)."""
+    s = _u8(sigs96)
+    if s.size % 96:
+        raise ValueError("signatures must be 96 bytes each")
+    B = s.size // 96
+    ids, G, mask = _group_args(group_ids, n_groups, include, B)
+    c = ctx or _native.context()
+    out = np.zeros(96 * max(G, 1), dtype=np.uint8)
+    ok = np.zeros(max(G, 1), dtype=np.uint8)
+    c.check(c.lib.bls_aggregate_grouped(c.h, _ptr(s), B, _ptr(ids), G, None if mask is None else _ptr(mask),
+                                        1 if subgroup_check else 0, _ptr(out), _ptr(ok)))
+    return _grouped_result(out[: 96 * G], ok[:G])
+
+
 def batch_work(ctx=None) -> tuple[int, int]:
     """(messages hashed, Miller pairs) of the last FAV / Verify batch prepared on the context: (B, B + 64)
     unshared, (M, M + 64) shared."""
@@ -541,6 +593,33 @@ class ResidentFavBatch:
         ok = self.check_partials(self.partial())
         self.finish(ok)
         return self.verdicts()
+
+    def aggregate_by_message(self, include=None, subgroup_check: bool = False) -> list:
+        """The M per-message aggregates of a shared-message batch that has been run: entry m is the sum of the
+        signatures of the items that sign table entry m and that the mask includes -- by default the batch's
+        last verdicts, read where finish left them in HBM -- or None for a message with no included item (or a
+        bad included signature).  bls_aggregate_grouped_dev on the batch's own signature buffer: nothing is
+        uploaded again but the mask a caller supplies."""
+        if self.msg_ids is None:
+            raise ValueError("aggregate_by_message needs a shared-message batch (msg_ids)")
+        c = self.ctx
+        mask_buf = None
+        if include is None:
+            d_mask = self.outs[self.last_job].ptr
+        else:
+            _, _, mask = _group_args(self.msg_ids, self.M, include, self.B)
+            mask_buf = DeviceBuffer(c, mask)
+            d_mask = mask_buf.ptr
+        out = DeviceBuffer(c, nbytes=97 * self.M)
+        try:
+            c.check(c.lib.bls_aggregate_grouped_dev(c.h, self.sigs.ptr, self.B, _ptr(self.msg_ids), self.M, d_mask,
+                                                    1 if subgroup_check else 0, out.ptr, out.ptr + 96 * self.M))
+            raw = out.to_host()
+        finally:
+            out.free()
+            if mask_buf is not None:
+                mask_buf.free()
+        return _grouped_result(raw[: 96 * self.M], raw[96 * self.M:])
 
     def free(self):
         for b in (self.idx, self.offs, self.msgs, self.sigs, *self.outs):

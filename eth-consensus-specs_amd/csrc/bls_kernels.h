@@ -123,6 +123,16 @@ struct SegRun;
 hipError_t launch_g1_seg_fold(hipStream_t st, int level, const SegRun* runs, uint32_t nruns, const uint32_t* items,
                               const int* status, const G1A* rP, const G1P* prev, G1P* tmp, G1P* gsum, int* ok);
 hipError_t launch_g2a_gather(hipStream_t st, size_t B, const G2A* H, const uint32_t* msg_id, G2A* out);
+// grouped signature aggregation (bls_segsum.hip): one level of the segmented G2 sum (bls_g2_segsum.h; level 0 reads
+// the decoded members a / ok through `items`, skipping those outside the nullable mask `include`; the levels above
+// read the partials `prev`; non-final runs write `tmp`, final runs gsum[group]), and the finish: G sums to
+// compressed bytes and ok (one inversion per 4 groups).  Partials are g2_seg_partial_bytes() each.
+struct G2SP;
+size_t g2_seg_partial_bytes();
+hipError_t launch_g2_seg_fold(hipStream_t st, int level, const SegRun* runs, uint32_t nruns, const uint32_t* items,
+                              const int* ok, const uint8_t* include, const G2A* a, const G2SP* prev, G2SP* tmp,
+                              G2SP* gsum);
+hipError_t launch_g2_seg_finish(hipStream_t st, size_t G, const G2SP* gsum, uint8_t* out96, uint8_t* out_ok);
 // nsel independent checks: out[b] = (FE(f[sel[b]]) == 1)
 hipError_t launch_final_check_sel(hipStream_t st, const Fp12* f, const uint32_t* sel, size_t nsel, int* out);
 hipError_t launch_fp12_chunk_prod(hipStream_t st, const Fp12* in, size_t n, int chunk, Fp12* out);

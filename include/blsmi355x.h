@@ -66,6 +66,38 @@ int bls_aggregate_verify(bls_ctx* ctx, const uint8_t* pks48, size_t n, const uin
  * list or an undecodable / non-G2 signature (the reference raises). */
 int bls_aggregate(bls_ctx* ctx, const uint8_t* sigs96, size_t n, uint8_t* out96);
 
+/* G Aggregate calls in one: group g is the items i with group_id[i] == g and
+ * (include == NULL || include[i] != 0), in any order.  Returns 1 or BLS_E_*.
+ *
+ * out_ok[g] = 1 and out96[96 g ..] = the compressed sum when group g has at
+ * least one included item and every included signature decodes and, with
+ * subgroup_check != 0, lies in G2; otherwise out_ok[g] = 0 and the 96 bytes
+ * are zero.  With subgroup_check = 1 that is, group by group, what
+ * bls_aggregate returns on the group's included signatures (code and bytes):
+ *   - the infinity encoding is a valid member and contributes the identity;
+ *   - a sum that is the identity (sigma and -sigma, or only infinity members)
+ *     is ok = 1 with bytes c0 00..;
+ *   - a bad member spoils only its own group;
+ *   - an excluded item's bytes are never judged and affect no output.
+ * subgroup_check = 0 decodes without the subgroup check, as bls_point_decode
+ * does -- for signatures a batch has already verified; the sum is still the
+ * correct sum of curve points (the additions are complete on E2(Fp2)).
+ *
+ * An id >= G, or G == 0 with B > 0, is BLS_E_ARG, refused before any device
+ * call.  B == 0 returns 1 with every out_ok 0.  The call uses scratch of its
+ * own: it may run between a FAV job's partial and finish without changing
+ * that job's verdicts. */
+int bls_aggregate_grouped(bls_ctx* ctx, const uint8_t* sigs96, size_t B, const uint32_t* group_id, size_t G,
+                          const uint8_t* include, int subgroup_check, uint8_t* out96, uint8_t* out_ok);
+/* The same on device pointers: d_sigs96 (96 B), d_include (B bytes, nullable;
+ * typically the verdict buffer bls_fav_job_finish_dev wrote), d_out96 (96 G)
+ * and d_ok (G) are device resident, group_id is a HOST array (free on return).
+ * It first waits for every job stream of the context, as bls_d2h does (a
+ * failing job's verdicts are written asynchronously); nothing passes through
+ * the host, and the results are complete after bls_d2h / bls_sync. */
+int bls_aggregate_grouped_dev(bls_ctx* ctx, const uint8_t* d_sigs96, size_t B, const uint32_t* group_id, size_t G,
+                              const uint8_t* d_include, int subgroup_check, uint8_t* d_out96, uint8_t* d_ok);
+
 /* _AggregatePKs  <- E/utils/bls.py:202-213 (eth_aggregate_pubkeys,
  * specs/altair/bls.md:36-52).  0 on empty list or any key failing
  * KeyValidate (the reference raises). */
