@@ -27,10 +27,11 @@ namespace bls {
 // one lane instead of 2 x 12 on a lane pair with the complete formulas), the base point parked in LDS.  Its
 // additions are incomplete, which is exact here: an exceptional step (an intermediate equal to +-sigma or the
 // identity) means sigma has order below 2^64, so sigma is not in G2 (order r) and is rejected -- as is an
-// identity result.
+// identity result.  The base sigma is affine, so the chain's five additions are mixed (j2q_add_aff: 7 + 4 Fp2
+// products instead of 11 + 5) and only x, y wait in LDS (56 words per lane).
 __global__ void __launch_bounds__(64) k_sig_lane2(size_t B, const int* gstat, int* status, const int* dstat,
                                                   const G1P* apk, const G2A* sig, const uint64_t* rsc, G1P* rPj) {
-  __shared__ uint32_t lds[84 * 64];
+  __shared__ uint32_t lds[56 * 64];  // sigma's affine x, y for the chain's mixed additions
   const unsigned nb = (unsigned)((B + 63) / 64);
   if (blockIdx.x < nb) {  // r_i apk_i = a apk_i + b phi(apk_i) in the redundant digit form, canonical output
     const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
@@ -50,7 +51,7 @@ __global__ void __launch_bounds__(64) k_sig_lane2(size_t B, const int* gstat, in
   }
   const G2A s = sig[i];
   bool exc = false;
-  const J2Q M = j2q_mul_xabs_lds(J2Q{fq2_unpack(s.x), fq2_unpack(s.y), fq2_unpack(fp2_one())}, exc, lds);
+  const J2Q M = j2q_mul_xabs_aff_lds(fq2_unpack(s.x), fq2_unpack(s.y), exc, lds);
   // sigma in G2  <=>  psi(sigma) == -[|x|] sigma:  conj(x) CX Z^2 == X,  conj(y) CY Z^3 == -Y,  Z != 0
   const Fp2 X = fq2_pack(M.x), Y = fq2_pack(M.y), Z = fq2_pack(M.z);
   const Fp2 zz = f2sqr(Z);
@@ -66,7 +67,7 @@ __global__ void __launch_bounds__(64) k_sig_lane2(size_t B, const int* gstat, in
 // The packed-form kernel it replaces kept a 3,696-B private segment and took ~5 ms for one per-call signature.
 // Signatures must be 4-byte aligned (every caller passes 96-B records of a device buffer).
 __global__ void __launch_bounds__(64) k_sig_validate(const uint8_t* sigs96, size_t n, G2A* out, int* ok) {
-  __shared__ uint32_t lds[84 * 64];
+  __shared__ uint32_t lds[56 * 64];  // sigma's affine x, y for the chain's mixed additions
   const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (i >= n) return;
   G2A s{fp2_zero(), fp2_zero(), true};
@@ -74,7 +75,7 @@ __global__ void __launch_bounds__(64) k_sig_validate(const uint8_t* sigs96, size
   int v = st == DEC_INFINITY ? 1 : 0;
   if (st == DEC_OK) {
     bool exc = false;
-    const J2Q M = j2q_mul_xabs_lds(J2Q{fq2_unpack(s.x), fq2_unpack(s.y), fq2_unpack(fp2_one())}, exc, lds);
+    const J2Q M = j2q_mul_xabs_aff_lds(fq2_unpack(s.x), fq2_unpack(s.y), exc, lds);
     const Fp2 X = fq2_pack(M.x), Y = fq2_pack(M.y), Z = fq2_pack(M.z);
     const Fp2 zz = f2sqr(Z);
     const Fp2 px = f2mul(f2mul(fp2_conj(s.x), PSI_CX), zz);

@@ -332,15 +332,12 @@ __global__ void __launch_bounds__(64) k_g2x_pre1t(size_t B, const int* status, F
   H2C_RELOAD_BARRIER();
   {
     const PP<Fp2> Q = pp2_load(r + HCF_Q);
-    const PP<Fp2> pq = pp_psi2x(Q);
     const PP<Fp2> t3{f2mul(Q.x, PSI2_CX), f2mul(Q.y, PSI2_CY), Q.z};  // psi^2(Q); psi^2(2Q) = 2 psi^2(Q)
-    pp_store1(r + HCF_C, pp_add(pp_dbl(t3), pp_neg2(pq)));          // psi^2(2Q) - psi(Q)
+    pp_store1(r + HCF_C, pp_add(pp_dbl(t3), pp_neg2(Q)));            // psi^2(2Q) - Q
   }
   H2C_RELOAD_BARRIER();
-  {
-    const PP<Fp2> mq = pp_add(pp2_load(r + HCF_M), pp_neg2(pp2_load(r + HCF_Q)));  // M - Q
-    pp_store1(r + HCF_C, pp_add(pp2_load(r + HCF_C), mq));
-  }
+  // C = psi^2(2Q) - psi(Q) + M - Q = (psi^2(2Q) - Q) - A: two additions, A = psi(Q) - M being staged already
+  pp_store1(r + HCF_C, pp_add(pp2_load(r + HCF_C), pp_neg2(pp2_load(r + HCF_A))));
   if (exc) flag[i] = 1;
 }
 
@@ -390,15 +387,11 @@ __global__ void __launch_bounds__(64) k_g2x_pre2(size_t B, const int* status, Fd
   H2C_RELOAD_BARRIER();
   {
     const PP<Fp2> Q = pp2_load(r + HCF_Q);
-    const PP<Fp2> pq = pp_psi2x(Q);
     const PP<Fp2> t3{f2mul(Q.x, PSI2_CX), f2mul(Q.y, PSI2_CY), Q.z};  // psi^2(Q); psi^2(2Q) = 2 psi^2(Q)
-    pp_store1(r + HCF_C, pp2_add(pp2_dbl(t3, hi), pp_neg2(pq), hi));    // psi^2(2Q) - psi(Q)
+    pp_store1(r + HCF_C, pp2_add(pp2_dbl(t3, hi), pp_neg2(Q), hi));     // psi^2(2Q) - Q
   }
   H2C_RELOAD_BARRIER();
-  {
-    const PP<Fp2> mq = pp2_add(pp2_load(r + HCF_M), pp_neg2(pp2_load(r + HCF_Q)), hi);  // M - Q
-    pp_store1(r + HCF_C, pp2_add(pp2_load(r + HCF_C), mq, hi));
-  }
+  pp_store1(r + HCF_C, pp2_add(pp2_load(r + HCF_C), pp_neg2(pp2_load(r + HCF_A)), hi));  // C = (psi^2(2Q) - Q) - A
   if (exc && !hi) flag[i] = 1;
 }
 

@@ -131,6 +131,87 @@ BLS_HD J2Q j2q_add(const J2Q& p, const J2Q& q, bool& exc) {
   return r;
 }
 
+// madd-2007-bl: p + (qx, qy) with the second point affine (Z2 = 1), 7 products + 4 squarings against the 11 + 5 of
+// j2q_add; incomplete in the same way: exc |= h = 0 (p = +-q) or p the identity, checked on canonical values.
+// Written in the bound-typed form (bls_fqb.h) on the chain's state bounds X < 1030p, Y < 650p, Z < 270p (L-form
+// digits), q canonical, so every product's columns and every subtraction constant are proved at compile time:
+// X3 < 12p, Y3 < 8p, Z3 < 14p out.
+BLS_HD J2Q j2q_add_aff(const J2Q& p, const Fq2& qx_, const Fq2& qy_, bool& exc) {
+  constexpr uint64_t LD = fqb_detail::MASK + 65;
+  const Fq2B<1030, LD> X1{{p.x.c0}, {p.x.c1}};
+  const Fq2B<650, LD> Y1{{p.y.c0}, {p.y.c1}};
+  const Fq2B<270, LD> Z1{{p.z.c0}, {p.z.c1}};
+  const Fq2B<1, fqb_detail::MASK> qx{{qx_.c0}, {qx_.c1}}, qy{{qy_.c0}, {qy_.c1}};
+  const auto z1z1 = sqr(Z1);
+  FQ_SEQ();
+  const auto u2 = qx * z1z1;
+  FQ_SEQ();
+  const auto s2 = (qy * Z1) * z1z1;
+  FQ_SEQ();
+  const auto h = norm(u2 - X1);
+  exc = exc || fp2_is_zero(fq2b_pack(h)) || fp2_is_zero(fq2_pack(p.z));
+  FQ_SEQ();
+  const auto hh = sqr(h);
+  FQ_SEQ();
+  const auto i4 = small<4>(hh);
+  const auto j = h * i4;
+  FQ_SEQ();
+  const auto rr = small<2>(norm(s2 - Y1));
+  const auto v = X1 * i4;
+  FQ_SEQ();
+  const auto x3 = norm(sqr(rr) - (j + small<2>(v)));
+  FQ_SEQ();
+  const auto y3 = norm(rr * norm(v - x3) - small<2>(Y1 * j));
+  FQ_SEQ();
+  const auto z3 = norm(sqr(norm(Z1 + h)) - (z1z1 + hh));
+  FQ_SEQ();
+  static_assert(decltype(x3.c0)::val <= 1030 && decltype(y3.c0)::val <= 650 && decltype(z3.c0)::val <= 270,
+                "the mixed addition leaves the chain's state bounds");
+  static_assert(decltype(x3.c0)::dig <= LD && decltype(y3.c0)::dig <= LD && decltype(z3.c0)::dig <= LD,
+                "the mixed addition leaves the chain's digit bound");
+  return J2Q{Fq2{x3.c0.x, x3.c1.x}, Fq2{y3.c0.x, y3.c1.x}, Fq2{z3.c0.x, z3.c1.x}};
+}
+
+// [|x|] (x, y) for an affine base: the five additions are mixed (j2q_add_aff)
+BLS_HD J2Q j2q_mul_xabs_aff(const Fq2& x, const Fq2& y, bool& exc) {
+  J2Q m{x, y, fq2_unpack(fp2_one())};
+#pragma unroll 1
+  for (int b = 62; b >= 0; --b) {
+    m = j2q_dbl(m);
+    if ((X_ABS >> b) & 1ull) m = j2q_add_aff(m, x, y, exc);
+  }
+  return m;
+}
+// the same with the base parked in LDS during the chain (lds: 56 words x 64 lanes, [word][lane]), as
+// j2q_mul_xabs_lds below does for a projective base
+__device__ __forceinline__ J2Q j2q_mul_xabs_aff_lds(const Fq2& x, const Fq2& y, bool& exc, uint32_t* lds) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t* xw = reinterpret_cast<const uint32_t*>(&x);
+  const uint32_t* yw = reinterpret_cast<const uint32_t*>(&y);
+#pragma unroll
+  for (int w = 0; w < 28; w++) {
+    lds[w * 64 + lane] = xw[w];
+    lds[(28 + w) * 64 + lane] = yw[w];
+  }
+  J2Q m{x, y, fq2_unpack(fp2_one())};
+#pragma unroll 1
+  for (int b = 62; b >= 0; --b) {
+    m = j2q_dbl(m);
+    if ((X_ABS >> b) & 1ull) {
+      Fq2 qx, qy;
+      uint32_t* qxw = reinterpret_cast<uint32_t*>(&qx);
+      uint32_t* qyw = reinterpret_cast<uint32_t*>(&qy);
+#pragma unroll
+      for (int w = 0; w < 28; w++) {
+        qxw[w] = lds[w * 64 + lane];
+        qyw[w] = lds[(28 + w) * 64 + lane];
+      }
+      m = j2q_add_aff(m, qx, qy, exc);
+    }
+  }
+  return m;
+}
+
 // [|x|] p with the base point parked in LDS during the chain (lds: 84 words x 64 lanes, [word][lane]): it is read
 // only by the 5 additions, and the 84 registers it held pushed an inlined chain past the register file (~300
 // spilled VGPRs) -- in registers the chain had to be a separate call with a ~1.8 KB private segment.

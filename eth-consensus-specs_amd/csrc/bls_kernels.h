@@ -75,8 +75,9 @@ hipError_t launch_msm_upairs(hipStream_t st, size_t B, const int* status, const 
                              const G2A* sig, uint32_t* scr, Fd* pts, const G1A* comb, G1A* P, G2A* Q, int* ok);
 // the same Miller values in two kernels (G2 lines, then f); L: miller_lines_u32(n) words of scratch
 constexpr int MILLER_NLINES = 68;  // 63 doublings + 5 additions (|x| = 0xd201000000010000)
-// Miller line records (k_miller_lines2 -> k_miller_acc4q): three Fp2 -- (l0, E ZZ, z3 ZZ) for a doubling, (l0, r,
-// z3) for an addition -- as 14-digit bound-typed values (bls_fqb.h FqB<ML_LV, ML_LD>: value < ML_LV p, digits <=
+// Miller line records (k_miller_lines2 -> k_miller_acc4q): three Fp2 (l0, l2, l3), the line l0 + l2 (-x_P) v
+// + l3 y_P v w up to an Fp2 factor -- (B - E, 3 J, H) for a doubling, (theta x_Q - lambda y_Q, theta, lambda) for an
+// addition, bls_miller_lines.h -- as 14-digit bound-typed values (bls_fqb.h FqB<ML_LV, ML_LD>: value < ML_LV p, digits <=
 // ML_LD), word w of line k of pair i at L[(k * ML_WORDS + w) * n + i]
 constexpr int ML_WORDS = 84;
 constexpr uint64_t ML_LV = 4096, ML_LD = 0x20000000ull + 64;

@@ -16,8 +16,8 @@ namespace bls {
 
 // The Miller loop in two kernels: the G2 side here (doubling/addition steps of T and the P-independent parts of
 // the line coefficients) and the f accumulation (k_miller_acc4q, bls_miller_pair.hip).  Lines are stored unscaled
-// -- (l0, E*ZZ, z3*ZZ) for a doubling, (l0, r, z3) for an addition -- and the accumulation multiplies the last two
-// by -x_P and y_P.  Layout: word w of line k of pair i at L[(k * ML_WORDS + w) * n + i] (bls_kernels.h), so the
+// -- (l0, l2, l3) of the homogeneous projective steps, bls_miller_lines.h -- and the accumulation multiplies the
+// last two by -x_P and y_P.  Layout: word w of line k of pair i at L[(k * ML_WORDS + w) * n + i] (bls_kernels.h), so the
 // 64 lanes of a wave read and write consecutive words; the words are the 14 digits of bound-typed values
 // FqB<ML_LV, ML_LD> (bls_fqb.h), which the accumulation multiplies without unpacking.
 //

@@ -155,8 +155,8 @@ __device__ __forceinline__ auto qq_line(const Fq6B<V, D>& own, bool h, bool q, c
   return norm(norm(m01) + sel(h, m1, f6v(m1)));
 }
 
-// one line's inputs on lane (h, q): l0 and the coefficient this lane scales (component q of E ZZ for h = 0, of
-// z3 ZZ for h = 1).  (Loading them one line ahead of use measured 3.72 ms per launch against 3.68 ms without, and
+// one line's inputs on lane (h, q): l0 and the coefficient this lane scales (component q of l2 for h = 0, of
+// l3 for h = 1).  (Loading them one line ahead of use measured 3.72 ms per launch against 3.68 ms without, and
 // the 512-register allocation it needed cost ~15 % of pipelined throughput.)
 struct LineIn {
   Fq2B<ML_LV, ML_LD> l0;
@@ -175,7 +175,7 @@ __device__ __forceinline__ LineIn ld_line(const uint32_t* Li, size_t n, bool h, 
   return r;
 }
 
-// a P-scaled record of k_miller_fused's line wave (mlines::Line1/Line2<true>): l0, l2 = E ZZ (-x_P), l3 = z3 ZZ y_P
+// a P-scaled record of k_miller_fused's line wave (mlines::Line1/Line2<true>): l0, l2 (-x_P), l3 y_P
 // (l2 and l3 are products -- mlines::scale -- so their words are N-form digits)
 struct LineS {
   Fq2B<ML_LV, ML_LD> l0;
@@ -195,14 +195,14 @@ __device__ __forceinline__ LineS ld_line_s(const uint32_t* Li, size_t n) {
   return r;
 }
 
-// the line's P factors, as q_line_p: l2 = E ZZ (-x_P), l3 = z3 ZZ y_P in N form
+// the line's P factors, as q_line_p: l2 (-x_P), l3 y_P in N form
 template <uint64_t VP, uint64_t DP>
 __device__ __forceinline__ void qq_line_p(const LineIn& in, const FqB<VP, DP>& pc, bool q, Fq2B<2, fqb_detail::MASK>& l2,
                                           Fq2B<2, fqb_detail::MASK>& l3) {
   const FqN mine = in.c * pc;
   const Fq2B<2, fqb_detail::MASK> m{bc<BQ0>(mine), bc<BQ1>(mine)};  // (component 0, component 1) of this h's product
-  l2 = bc2<BH0>(m);                                                  // E ZZ (-x_P), from the h = 0 lanes
-  l3 = bc2<BH1>(m);                                                  // z3 ZZ y_P, from the h = 1 lanes
+  l2 = bc2<BH0>(m);                                                  // l2 (-x_P), from the h = 0 lanes
+  l3 = bc2<BH1>(m);                                                  // l3 y_P, from the h = 1 lanes
 }
 
 }  // namespace
@@ -303,8 +303,8 @@ namespace {
 
 constexpr int BL0 = 0x00, BL1 = 0x55, BL2 = 0xAA, BL3 = 0xFF;
 
-// one line on this lane: l0, l2 = E ZZ (-x_P), l3 = z3 ZZ y_P; the lane scales its h's coefficient (both
-// components: h = 0 E ZZ by -x_P, h = 1 z3 ZZ by y_P) and takes the other from its h partner.  A pair that is not
+// one line on this lane: l0, l2 (-x_P), l3 y_P; the lane scales its h's coefficient (both
+// components: h = 0 l2 by -x_P, h = 1 l3 by y_P) and takes the other from its h partner.  A pair that is not
 // live is the line 1.
 struct LineF {
   Fq2B<ML_LV, ML_LD> l0;
