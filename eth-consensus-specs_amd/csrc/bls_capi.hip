@@ -1340,11 +1340,15 @@ static int fav_prepare(bls_ctx* ctx, const uint32_t* d_idx, const uint64_t* d_of
   else
     PROF2(1, sd, launch_sig_decode(sd, B, d_msgs, d_sigs, d_seed, sig, rsc, dstat));
   HIPCK(hipEventRecord(J.ev_sig, sd));
-  // the registry gather: the complete-formula kernel (k_fav_gather_q, 108 registers: four waves per SIMD, beside the
-  // one-wave lane kernels whose register files it fits into), or with BLS_GATHER=affine (read per batch) affine
-  // additions sharing one inversion per level (bls_gather_aff.hip: 42 % fewer VALU instructions per aggregate, but
-  // 234 registers, so it holds its SIMDs alone or in pairs; C2 measured the same within +-1 % over three A/Bs,
-  // profiles/r06_gather_ab.txt); aggregates with an exceptional pair are redone by the complete formulas
+  // the registry gather: the complete-formula kernel (k_fav_gather_q; 204 registers by the compiler's report, two
+  // waves per SIMD), or with BLS_GATHER=affine (read per batch) affine additions sharing one inversion per level
+  // (bls_gather_aff.hip: 42 % fewer VALU instructions per aggregate, 234 registers; C2 measured the same within
+  // +-1 % over three A/Bs, profiles/r06_gather_ab.txt); aggregates with an exceptional pair are redone by the
+  // complete formulas.  The gather is not free: 2,500 waves of a C2 batch, 30 % of the instructions the batch issues
+  // and about a quarter of a C2 step (C2 / C4 = 1.39 per item, the work model's 1.38).  The affine
+  // A/B did not show that because its waves held their SIMDs alone, 28.5 % of the time waiting on HBM level lists
+  // (~790 exclusive SIMD-ms, as much as it saved); cutting the complete kernel's own instructions by 15.8 % (one
+  // reduction per output coordinate, bls_fq_g1.h) gained C2 3.1 % (profiles/g1dot_ab.txt).
   const char* gv = getenv("BLS_GATHER");
   const size_t gw = (gv && !strcmp(gv, "affine")) ? fav_gather_aff_words(B) : 0;
   if (gw) {

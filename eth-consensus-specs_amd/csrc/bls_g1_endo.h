@@ -15,15 +15,15 @@ namespace bls {
 
 // a A + b phi(A).  A: N- or L-form coordinates (digits <= 2^29 + 2^4) with values below 4p, any point of the curve
 // including the identity (complete formulas, no exceptional case).  Bounds of the table operand T of g1q_add
-// (its first operand is always a g1q_dbl output, X, Y < 4p, Z < 2p in L form):
+// (its first operand is always a g1q_dbl output: X < 4p with digits <= 2^29, Y, Z in N form):
 //   T.x in {X, beta X, beta^2 X}: products are N form, < 2p;  T.z = Z;
 //   T.y in {Y, -Y}, -Y = 64p - Y digit-wise (fq_sub from zero: Q29_K1's digits are >= any N/L digit), normalised
 //   to L form (digits <= 2^29 + 1), value <= 64p.
 // Then every product of g1q_add stays far below p R (R / p ~ 2^25.3): the largest is
 // (p.x + p.y)(T.x + T.y) < 8p x 66p, and (p.y + p.z)(T.y + T.z) < 6p x 68p; operand digits are <= 2^30 + 2^5 on
-// both sides (sums of two L forms), inside fq_mul's column bound.  The outputs are those of g1q_add on L-form
-// inputs (X < 66p, Y, Z < 4p, L form), which g1q_dbl takes.  The digit is chosen by selects and the addition is
-// always computed: in a 64-lane wave some lane has a non-zero digit at every step.
+// both sides (sums of two L forms), inside fq_mul's column bound; g1q_add proves all of this at compile time for
+// any operand coordinate below 66p.  Its outputs are in N form (< 2p), which g1q_dbl takes.  The digit is chosen by
+// selects and the addition is always computed: in a 64-lane wave some lane has a non-zero digit at every step.
 BLS_HD G1Q g1q_mul_endo(const G1Q& A, uint32_t a, uint32_t b) {
   const Fq beta = fq_unpack(FP_BETA);
   const Fq x1 = fq_mul(A.x, beta);

@@ -93,7 +93,8 @@ namespace bls {
 
 // The fold of one run, in the redundant digit form with the complete formulas of bls_fq_g1.h, everything in
 // registers.  Bounds: the accumulator starts at the identity (0 : 1 : 0) in N form and is from then on an output
-// of g1q_add_aff / g1q_add, the L-form accumulator of bls_fq_g1.h (digits <= 2^29 + 2^4; X < 66p, Y, Z < 4p).
+// of g1q_add_aff (N form, < 2p) or of g1q_add_mem below (L form: digits <= 2^29 + 2^4; X < 66p, Y, Z < 4p), both
+// inside the accumulator contract of bls_fq_g1.h.
 //   level 0: the operand is an affine r_i apk_i, canonical (< p, N form) -- exactly k_fav_gather_q's inner loop,
 //     whose largest product is (x2 + y2)(X + Y) < 2p x 70p;
 //   above: the operand q is a partial stored canonical (fq_pack) and unpacked, X, Y, Z < p in N form, so
@@ -118,10 +119,12 @@ BLS_HD G1Q seg_fold_items(const SegRun& r, const uint32_t* items, const int* sta
   return acc;
 }
 
-// g1q_add(p, *q) with q in memory: the same products in the same forms, ordered so that each of its three cross
-// terms reads the two coordinates of q it needs again instead of holding all of q (42 registers) across the
-// formula -- with both operands in registers the kernel needs more than half a SIMD's register file.  On the
-// device the pointer passes through an empty asm between the terms, so the reads are issued again (L2 hits).
+// p + *q with q in memory: the complete addition (RCB alg. 7) in its own statement, one Montgomery reduction per
+// product and the two products of a coordinate combined after both are reduced (g1q_add of bls_fq_g1.h forms each
+// coordinate with one reduction; the residues are the same), ordered so that each of its three cross terms reads
+// the two coordinates of q it needs again instead of holding all of q (42 registers) across the formula -- with
+// both operands in registers the kernel needs more than half a SIMD's register file.  On the device the pointer
+// passes through an empty asm between the terms, so the reads are issued again (L2 hits).
 BLS_HD const G1P* seg_reread(const G1P* q) {
 #ifdef __HIP_DEVICE_COMPILE__
   asm volatile("" : "+v"(q));
