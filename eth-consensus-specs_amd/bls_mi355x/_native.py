@@ -72,6 +72,11 @@ _SIGS = {
     "bls_verify_batch_indexed_shared": (_ip, [_vp, _vp, _sz, _u8p, _sz, _vp, _u8p, _vp]),
     "bls_fav_job_submit_shared_dev": (_ip, [_vp, _ip, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _u8p]),
     "bls_last_batch_work": (_ip, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "bls_committees_load": (_ip, [_vp, _vp, _vp, _sz]),
+    "bls_committees_count": (_sz, [_vp]),
+    "bls_fav_batch_committee_bits": (_ip, [_vp, _vp, _vp, _vp, _vp, _sz, _u8p, _sz, _vp, _u8p, _ip, _vp]),
+    "bls_fav_job_submit_bits_dev": (_ip, [_vp, _ip, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _ip, _u8p]),
+    "bls_last_gather_work": (_ip, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "bls_aggregate_verify_batch": (_ip, [_vp, _u8p, _u8p, _vp, _vp, _sz, _u8p, _vp]),
     "bls_registry_append": (_ip, [_vp, _u8p, _sz, _vp]),
     "bls_signing_roots": (_ip, [_vp, _u8p, _u8p, _sz, _sz, _vp]),

@@ -226,6 +226,132 @@ def verify_batch_shared(indices, table, msg_ids, sigs96, ctx=None) -> np.ndarray
     return out.astype(bool)
 
 
+class Committees:
+    """HBM-resident committee table of one context (bls_committees_load): every committee a list of registry
+    indices, fixed for an epoch.  The device keeps each committee's key sum, so that a nearly full aggregate costs
+    its absentees instead of its participants (fast_aggregate_verify_batch_bits).  The table belongs to the
+    registry it was loaded on: Registry.load / generate make it stale (the bits calls then raise), append keeps
+    it."""
+
+    def __init__(self, ctx: _native.Context | None = None):
+        self.ctx = ctx or _native.context()
+        self.sizes = np.zeros(0, dtype=np.uint64)
+
+    def load(self, index_lists) -> "Committees":
+        """index_lists: one sequence of registry indices per committee, or the tuple (flat, offsets) with
+        committee c = flat[offsets[c]: offsets[c + 1]].  Replaces any earlier table of the context."""
+        if isinstance(index_lists, tuple) and len(index_lists) == 2:
+            flat = np.ascontiguousarray(index_lists[0], dtype=np.uint32)
+            offs = np.ascontiguousarray(index_lists[1], dtype=np.uint64)
+        else:
+            lists = [np.asarray(c, dtype=np.uint32).reshape(-1) for c in index_lists]
+            flat = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, np.uint32), dtype=np.uint32)
+            offs = offsets_from_lengths([c.size for c in lists])
+        if offs.ndim != 1 or offs.size < 1 or np.any(offs[1:] < offs[:-1]) or int(offs[-1]) > flat.size:
+            raise ValueError("offsets must be non-decreasing and end inside the index array")
+        c = self.ctx
+        c.check(c.lib.bls_committees_load(c.h, _ptr(flat), _ptr(offs), offs.size - 1))
+        self.sizes = np.diff(offs)
+        return self
+
+    def __len__(self):
+        return int(self.sizes.size)
+
+
+def bits_from_bitlist(ssz_bytes, n: int) -> bytes:
+    """The ceil(n / 8) participation bytes of a serialized SSZ Bitlist of n bits (aggregation_bits): the
+    delimiter bit at position n is checked and stripped."""
+    raw = bytes(ssz_bytes)
+    if n < 0 or len(raw) != n // 8 + 1 or raw[-1] >> (n % 8) != 1:
+        raise ValueError("not a serialized Bitlist of that length")
+    body = bytearray(raw[: (n + 7) // 8])
+    if n % 8:
+        body[-1] &= (1 << (n % 8)) - 1
+    return bytes(body)
+
+
+BITS_MODES = {"auto": 0, "direct": 1, "complement": 2}
+
+
+def _bits_args(committees: Committees, committee_ids, bits, B: int):
+    """(comm_ids u32, comm_offs u64, bit bytes u8, bit_offs u64) of a bits batch of B items, checked on the host
+    (ValueError before any device call): every id names a committee of the table, and item b carries exactly
+    ceil(n_b / 8) bytes -- or a bool array of n_b entries, packed here -- for the n_b members of its committees."""
+    if len(committee_ids) != B or len(bits) != B:
+        raise ValueError("need one committee id (or list of ids) and one bitfield per item")
+    C = len(committees)
+    per_item = []
+    for ids in committee_ids:
+        a = np.asarray(ids)
+        if a.size and a.dtype.kind not in "ui":
+            raise ValueError("committee ids must be integers")
+        a = a.reshape(-1)
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= C):
+            raise ValueError("committee id out of range")
+        per_item.append(a.astype(np.uint32))
+    comm_offs = offsets_from_lengths([a.size for a in per_item])
+    comm_ids = np.ascontiguousarray(np.concatenate(per_item) if per_item else np.zeros(0, np.uint32), dtype=np.uint32)
+    packed = []
+    for a, bf in zip(per_item, bits):
+        n = int(committees.sizes[a].sum()) if a.size else 0
+        if isinstance(bf, (bytes, bytearray, memoryview)):
+            raw = bytes(bf)
+        else:
+            arr = np.asarray(bf)
+            if arr.dtype != np.bool_ or arr.ndim != 1 or arr.size != n:
+                raise ValueError("a bit array needs one bool per member of the item's committees")
+            raw = np.packbits(arr, bitorder="little").tobytes()
+        if len(raw) != (n + 7) // 8:
+            raise ValueError("an item needs ceil(n / 8) bytes of bits for the n members of its committees")
+        packed.append(raw)
+    bit_offs = offsets_from_lengths([len(r) for r in packed])
+    return comm_ids, comm_offs, np.frombuffer(b"".join(packed), dtype=np.uint8), bit_offs
+
+
+def _mode(mode) -> int:
+    if mode not in BITS_MODES:
+        raise ValueError('mode must be "auto", "direct" or "complement"')
+    return BITS_MODES[mode]
+
+
+def fast_aggregate_verify_batch_bits(committees: Committees, committee_ids, bits, msgs32, sigs96, msg_ids=None,
+                                     table=None, mode: str = "auto", ctx=None) -> np.ndarray:
+    """B FastAggregateVerify calls whose signers are (committees, participation bits), as an attestation carries
+    them: committee_ids[b] is a committee number or a list of them, bits[b] the item's bitfield over their
+    concatenated members (bytes in SSZ bit order without the delimiter -- see bits_from_bitlist -- or a bool
+    array).  Same verdicts as fast_aggregate_verify_batch on the expanded indices; with msg_ids, as
+    fast_aggregate_verify_batch_shared over `table` (default: msgs32 is the table).  mode: "auto" subtracts the
+    absentees from the committees' cached sums when that adds fewer points; "direct" / "complement" force a form
+    (tests, measurements)."""
+    B = len(committee_ids)
+    m = _mode(mode)
+    comm_ids, comm_offs, raw, bit_offs = _bits_args(committees, committee_ids, bits, B)
+    s = _u8(sigs96)
+    if s.size != 96 * B:
+        raise ValueError("need one 96-byte signature per aggregate")
+    if msg_ids is not None:
+        t, M, ids = _shared_args(msgs32 if table is None else table, msg_ids, B)
+        ids_p = _ptr(ids)
+    else:
+        t, M, ids_p = _u8(msgs32), 0, None
+        if t.size != 32 * B:
+            raise ValueError("need one 32-byte message per aggregate")
+    c = ctx or committees.ctx
+    out = np.zeros(B, dtype=np.uint8)
+    c.check(c.lib.bls_fav_batch_committee_bits(c.h, _ptr(comm_ids), _ptr(comm_offs), _ptr(raw), _ptr(bit_offs), B,
+                                               t.tobytes(), M, ids_p, s.tobytes(), m, _ptr(out)))
+    return out.astype(bool)
+
+
+def gather_work(ctx=None) -> tuple[int, int]:
+    """(points added, complement items) of the last bits batch prepared on the context: the keys its gather
+    added plus the committee sums of its complement items, and how many items took the complement form."""
+    c = ctx or _native.context()
+    pts, cmpl = ctypes.c_uint64(), ctypes.c_uint64()
+    c.check(c.lib.bls_last_gather_work(c.h, ctypes.byref(pts), ctypes.byref(cmpl)))
+    return int(pts.value), int(cmpl.value)
+
+
 def _group_args(group_ids, n_groups, include, B: int) -> tuple[np.ndarray, int, np.ndarray | None]:
     """(ids as uint32, G, mask as u8 or None) of a grouped aggregation of B signatures, checked on the host
     (ValueError before any device call): one integer id in [0, G) per signature, one mask byte per signature."""
@@ -451,14 +577,26 @@ class ResidentFavBatch:
     final-exponentiated by ``check_partials``; ``finish()`` writes verdicts.
     """
 
-    def __init__(self, indices, offsets, msgs32, sigs96, ctx=None, chunks: int = 1, msg_ids=None):
+    def __init__(self, indices, offsets, msgs32, sigs96, ctx=None, chunks: int = 1, msg_ids=None, committees=None,
+                 committee_ids=None, bits=None, mode: str = "auto"):
         """chunks > 1 splits the batch into that many equal sub-batches (uniform committee size only), each
         submitted as its own FAV job: a pass over the batch is `chunks` jobs (large shards, e.g. the C4 firehose,
         stay within one job's scratch).
 
         msg_ids (one per item): the items share messages -- msgs32 is then the message table and item b signs
         entry msg_ids[b] (group_messages); the batch runs through the job API (run_pipelined / run), one hash and
-        one Miller pair per table entry.  Needs chunks == 1."""
+        one Miller pair per table entry.  Needs chunks == 1.
+
+        committees / committee_ids / bits (indices and offsets None): the items are (committees, participation
+        bits) over a Committees table, as in fast_aggregate_verify_batch_bits; only the bit bytes, messages and
+        signatures are resident, and every chunk (B divisible by chunks, any item sizes) is submitted through
+        bls_fav_job_submit_bits_dev in the given mode.  The batch runs through the job API."""
+        self.committees = committees
+        if committees is not None:
+            self._init_bits(committees, committee_ids, bits, msgs32, sigs96, ctx, chunks, msg_ids, mode)
+            return
+        if committee_ids is not None or bits is not None:
+            raise ValueError("committee_ids and bits need a committees table")
         offs = np.ascontiguousarray(offsets, dtype=np.uint64)
         self.B = int(offs.size - 1)
         self.chunks = max(1, int(chunks))
@@ -485,9 +623,38 @@ class ResidentFavBatch:
         self.last_job = 0
         self._chunk_job = [0] * self.chunks  # job whose buffer holds each chunk's latest verdicts
 
+    def _init_bits(self, committees, committee_ids, bits, msgs32, sigs96, ctx, chunks, msg_ids, mode):
+        if committee_ids is None or bits is None:
+            raise ValueError("a committees table needs committee_ids and bits")
+        self.B = len(committee_ids)
+        self.chunks = max(1, int(chunks))
+        self.mode = _mode(mode)
+        self.comm_ids, self.comm_offs, raw, self.bit_offs = _bits_args(committees, committee_ids, bits, self.B)
+        self.msg_ids, self.M = None, 0
+        if msg_ids is not None:
+            if self.chunks != 1:
+                raise ValueError("a shared-message batch needs chunks == 1")
+            _, self.M, self.msg_ids = _shared_args(msgs32, msg_ids, self.B)
+        elif _u8(msgs32).size != 32 * self.B:
+            raise ValueError("need one 32-byte message per aggregate")
+        if _u8(sigs96).size != 96 * self.B:
+            raise ValueError("need one 96-byte signature per aggregate")
+        if self.B % self.chunks:
+            raise ValueError("chunks > 1 needs B divisible by chunks")
+        self.cb, self.n = self.B // self.chunks, None
+        self.ctx = ctx or committees.ctx
+        self.idx = self.offs = None
+        self.bits = DeviceBuffer(self.ctx, raw)
+        self.msgs = DeviceBuffer(self.ctx, _u8(msgs32))
+        self.sigs = DeviceBuffer(self.ctx, _u8(sigs96))
+        self.outs = [DeviceBuffer(self.ctx, nbytes=self.B) for _ in range(FAV_JOBS)]
+        self.out = self.outs[0]
+        self.last_job = 0
+        self._chunk_job = [0] * self.chunks
+
     def partial(self, seed32: bytes | None = None) -> bytes:
-        if self.chunks > 1 or self.msg_ids is not None:
-            raise ValueError("a chunked or shared-message batch runs through the job API (run_pipelined)")
+        if self.chunks > 1 or self.msg_ids is not None or self.committees is not None:
+            raise ValueError("a chunked, shared-message or bits batch runs through the job API (run_pipelined)")
         seed = seed32 if seed32 is not None else os.urandom(32)
         buf = ctypes.create_string_buffer(576)
         c = self.ctx
@@ -513,6 +680,17 @@ class ResidentFavBatch:
 
     def submit(self, job: int, seed32: bytes, chunk: int = 0) -> None:
         c = self.ctx
+        if self.committees is not None:
+            # the chunk's slices of the host offset tables index the whole comm_ids array and the whole bits buffer
+            lo = chunk * self.cb
+            co = self.comm_offs[lo: lo + self.cb + 1]
+            bo = self.bit_offs[lo: lo + self.cb + 1]
+            shared = self.msg_ids is not None
+            c.check(c.lib.bls_fav_job_submit_bits_dev(
+                c.h, job, _ptr(self.comm_ids), _ptr(co), self.bits.ptr, _ptr(bo), self.cb,
+                self.msgs.ptr + (0 if shared else 32 * lo), self.M, _ptr(self.msg_ids) if shared else None,
+                self.sigs.ptr + 96 * lo, self.mode, seed32))
+            return
         idx, msgs, sigs, _ = self._chunk_ptrs(chunk)
         if self.msg_ids is not None:
             c.check(c.lib.bls_fav_job_submit_shared_dev(c.h, job, idx, self.offs.ptr, self.cb, msgs, self.M,
@@ -537,7 +715,7 @@ class ResidentFavBatch:
 
     def job_finish(self, job: int, batch_ok: bool, chunk: int = 0) -> None:
         c = self.ctx
-        lo = self._chunk_ptrs(chunk)[3]
+        lo = chunk * self.cb
         c.check(c.lib.bls_fav_job_finish_dev(c.h, job, 1 if batch_ok else 0, self.outs[job].ptr + lo))
         self.last_job = job
         self._chunk_job[chunk] = job
@@ -587,7 +765,7 @@ class ResidentFavBatch:
                               ).astype(bool)
 
     def run(self) -> np.ndarray:
-        if self.msg_ids is not None:
+        if self.msg_ids is not None or self.committees is not None:
             self.run_pipelined([os.urandom(32)])
             return self.verdicts()
         ok = self.check_partials(self.partial())
@@ -622,8 +800,9 @@ class ResidentFavBatch:
         return _grouped_result(raw[: 96 * self.M], raw[96 * self.M:])
 
     def free(self):
-        for b in (self.idx, self.offs, self.msgs, self.sigs, *self.outs):
-            b.free()
+        for b in (self.idx, self.offs, getattr(self, "bits", None), self.msgs, self.sigs, *self.outs):
+            if b is not None:
+                b.free()
 
 
 class Profiler:

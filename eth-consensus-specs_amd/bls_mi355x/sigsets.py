@@ -159,6 +159,7 @@ class _Set:
     signature: bytes = b""
     indices: np.ndarray | None = None
     malformed: bool = False
+    cbits: tuple | None = None  # (committee ids, participation bits) of a set given as an attestation carries it
 
 
 def _b(x) -> bytes:
@@ -168,14 +169,19 @@ def _b(x) -> bytes:
 class SignatureSets:
     """Collects verify calls; ``verify()`` checks them in as few device batches as possible."""
 
-    def __init__(self, registry: _batch.Registry | None = None, ctx=None, share_messages: bool = False):
-        """share_messages: when the indexed sets hold fewer distinct messages than sets (the attestations of a
+    def __init__(self, registry: _batch.Registry | None = None, ctx=None, share_messages: bool = False,
+                 committees: _batch.Committees | None = None):
+        """committees: the context's committee table; sets added with ``add_fast_aggregate_verify_bits`` go through
+        ``batch.fast_aggregate_verify_batch_bits`` against it (with share_messages, its msg_ids form).
+
+        share_messages: when the indexed sets hold fewer distinct messages than sets (the attestations of a
         slot, the aggregates of a committee, sync-committee messages), check them through
         ``batch.fast_aggregate_verify_batch_shared``: one hash_to_G2 and one Miller pair per distinct message.
         Same verdicts; off by default."""
         self.registry = registry
         self.ctx = ctx
         self.share_messages = share_messages
+        self.committees = committees
         self.sets: list[_Set] = []
         self.eager = 0  # verify calls inside deferred() that ran at once (result not asserted)
 
@@ -221,6 +227,22 @@ class SignatureSets:
         except Exception:
             return self._add(_Set(FAV, malformed=True))
 
+    def add_fast_aggregate_verify_bits(self, committee_ids, bits, message32, signature) -> int:
+        """The signers as an attestation holds them: committee numbers of the collector's ``committees`` table and
+        the participation bits over their members (``batch.fast_aggregate_verify_batch_bits``).  A set that call
+        would refuse -- an unknown committee, the wrong number of bit bytes, a message other than 32 bytes or a
+        signature other than 96 -- is False, as a per-call verify that raises is."""
+        if self.committees is None:
+            raise ValueError("add_fast_aggregate_verify_bits needs SignatureSets(committees=...)")
+        try:
+            msg, sig = _b(message32), _b(signature)
+            ids, _, raw, _ = _batch._bits_args(self.committees, [committee_ids], [bits], 1)
+            if len(msg) != 32 or len(sig) != 96:
+                raise ValueError("need a 32-byte message and a 96-byte signature")
+            return self._add(_Set(FAV, [], [msg], sig, cbits=(ids, raw.tobytes())))
+        except Exception:
+            return self._add(_Set(FAV, malformed=True))
+
     def add_verify(self, pubkey, message, signature) -> int:
         try:
             return self._add(self._wellformed(_Set(VERIFY, [_b(pubkey)], [_b(message)], _b(signature))))
@@ -246,7 +268,7 @@ class SignatureSets:
         """(indexed, av, single): set ids per execution route, plus the indices of the indexed ones."""
         indexed, av, single = [], [], []
         for i, s in enumerate(self.sets):
-            if s.malformed:
+            if s.malformed or s.cbits is not None:  # bits sets have their own route (verify)
                 continue
             if s.kind in (FAV, VERIFY) and len(s.messages[0]) == 32 and len(s.signature) == 96 and s.pubkeys:
                 idx = self._resident(s)
@@ -276,6 +298,19 @@ class SignatureSets:
                 v = _batch.fast_aggregate_verify_batch(idx, offs, msgs, sigs, ctx=self.ctx)
             for i, ok in zip(ids, v):
                 out[i] = bool(ok)
+        bits_ids = [i for i, s in enumerate(self.sets) if s.cbits is not None and not s.malformed]
+        if bits_ids:
+            sets = [self.sets[i] for i in bits_ids]
+            msgs = b"".join(s.messages[0] for s in sets)
+            sigs = b"".join(s.signature for s in sets)
+            table, mids = _batch.group_messages(msgs) if self.share_messages else (msgs, None)
+            if mids is None or len(table) == len(msgs):
+                table, mids = msgs, None
+            v = _batch.fast_aggregate_verify_batch_bits(self.committees, [s.cbits[0] for s in sets],
+                                                        [s.cbits[1] for s in sets], table, sigs, msg_ids=mids,
+                                                        ctx=self.ctx)
+            for i, ok in zip(bits_ids, v):
+                out[i] = bool(ok)
         if av:
             sets = [self.sets[i] for i in av]
             v = _batch.aggregate_verify_batch([s.pubkeys for s in sets], [s.messages for s in sets],
@@ -298,7 +333,8 @@ class SignatureSets:
 
 
 @contextlib.contextmanager
-def deferred(registry: _batch.Registry | None = None, ctx=None, check: bool = True, share_messages: bool = False):
+def deferred(registry: _batch.Registry | None = None, ctx=None, check: bool = True, share_messages: bool = False,
+             committees: _batch.Committees | None = None):
     """Within the block, ``bls_mi355x.bls.Verify/FastAggregateVerify/AggregateVerify`` calls whose result is
     asserted record their arguments into a ``SignatureSets`` and return True (every other call runs at once,
     see the module docstring); at exit the sets are verified in batches and, with ``check``, an
@@ -306,7 +342,7 @@ def deferred(registry: _batch.Registry | None = None, ctx=None, check: bool = Tr
     verdicts after the block).  share_messages: see ``SignatureSets``."""
     from . import bls as shim
 
-    sets = SignatureSets(registry, ctx, share_messages)
+    sets = SignatureSets(registry, ctx, share_messages, committees)
     prev = shim._collector
     shim._collector = sets
     try:

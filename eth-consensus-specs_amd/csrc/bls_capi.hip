@@ -15,6 +15,7 @@
 #include "bls_kernels.h"
 #define BLS_SEGSUM_PLAN_ONLY  // the host plan of the segmented G1 sum; its kernels are in bls_segsum.hip
 #include "bls_g1_segsum.h"
+#include "bls_g1_bits.h"
 
 using namespace bls;
 
@@ -50,6 +51,10 @@ enum Slot {
   // finish calls): staged signatures, mask and outputs of the host-buffer call, the decoded members and their ok,
   // the fold's runs, sorted item list, two partial arrays and the group sums
   S_AGG_IN, S_AGG_INC, S_AGG_OUT, S_AGG_A, S_AGG_OK, S_AGG_RUN, S_AGG_IT, S_AGG_PA, S_AGG_PB, S_AGG_SUM,
+  // committee-bitfield batches (fav_prepare with bits): the job's host tables in one piece (the three offset tables
+  // -- committees | bit bytes | list slots, B + 1 each -- then the items' committee ids), the expanded index lists
+  // and the item records
+  S_BTAB, S_BLIST, S_BITEM,
   NSLOT
 };
 
@@ -99,6 +104,16 @@ struct Job {
   bool fav_shared = false;
   SegPlan seg;
   std::vector<uint32_t> seg_ids;
+  // the prepared batch's items are (committees, bits) (fav_prepare with bits): the host tables its upload reads, in
+  // pinned memory so that the copy never holds the submitting thread -- comm_offs | bit_offs | slot_offs (B + 1
+  // u64 each), then the items' committee ids (u32) -- refilled only after the last upload has passed ev_bits;
+  // bits_B / bits_items: the batch bls_last_gather_work reads back
+  uint64_t* bits_tab = nullptr;
+  size_t bits_tab_cap = 0, bits_tab_bytes = 0, bits_B = 0;
+  hipEvent_t ev_bits = nullptr;
+  bool bits_up_pending = false;
+  const BitsItem* bits_items = nullptr;
+  std::vector<uint64_t> bits_n;  // bits_plan's member counts
   // last bisection fallback: final-exponentiation checks and rounds (levels); the checks of a FAV bisection are
   // counted on the device (bis_dev_checks, read after the job's stream by bls_last_fallback_stats)
   uint64_t bis_checks = 0, bis_rounds = 0;
@@ -133,6 +148,17 @@ struct bls_ctx {
   size_t reg_n = 0;
   size_t reg_cap = 0;  // entries allocated (bls_registry_append grows it)
   uint64_t reg_gen = 0;  // bumped whenever the table is replaced (load / generate)
+  // committee table (bls_committees_load, HBM resident): member lists ctab_idx[ctab_offs[c] .. ctab_offs[c + 1]),
+  // csum[c] their keys' projective sum and cstat[c] = 1 iff every member was in range and valid at load; the
+  // offsets' host copy sizes the items of a bits batch; ctab_gen: the registry generation the sums belong to
+  uint32_t* ctab_idx = nullptr;
+  uint64_t* ctab_offs = nullptr;
+  G1P* ctab_sum = nullptr;
+  int* ctab_stat = nullptr;
+  std::vector<uint64_t> ctab_offs_h;
+  bool ctab_loaded = false;
+  uint64_t ctab_gen = 0;
+  Job* work_job = nullptr;  // the job whose bits batch bls_last_gather_work reports
   // test hook (bls_test_force_h2c_fallback): items whose hash_to_G2 is routed to k_h2c_fallback regardless of
   // the lane kernels' flags; null in every product use
   int* force_fb = nullptr;
@@ -154,7 +180,7 @@ struct bls_ctx {
 
 static const char* const PROF_NAMES[] = {"fav_gather", "sig_decode", "fav_hash", "g2_sum",        "sig_pair", "miller",
                                          "fp12_prod",  "final_exp",  "fav_finish", "partials_prod", "sig_vm",
-                                         "msm",        "miller_lines", "key_validate"};
+                                         "msm",        "miller_lines", "key_validate", "bits_expand"};
 static const int PROF_N = sizeof(PROF_NAMES) / sizeof(PROF_NAMES[0]);
 
 namespace {
@@ -458,6 +484,7 @@ static bool job_init(Job& J, int prio_hi, int streams) {
          hipEventCreateWithFlags(&J.ev_own, hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&J.ev_comm, hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&J.ev_cv, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&J.ev_bits, hipEventDisableTiming) == hipSuccess &&
          hipHostMalloc((void**)&J.h_own, 2 * sizeof(int), hipHostMallocDefault) == hipSuccess &&
          hipHostMalloc((void**)&J.h_partial, 576, hipHostMallocDefault) == hipSuccess;
 }
@@ -468,11 +495,12 @@ static void job_destroy(Job& J) {
     if (s) (void)hipStreamSynchronize(s);
   for (auto& b : J.buf)
     if (b.p) (void)hipFree(b.p);
-  hipEvent_t es[13] = {J.ev_fork, J.ev_join, J.ev_sig, J.ev_msm, J.ev_gather, J.ev_partial, J.ev_h2c,
-                       J.ev_fb,   J.ev_fe,   J.ev_bis, J.ev_own, J.ev_comm,   J.ev_cv};
+  hipEvent_t es[14] = {J.ev_fork, J.ev_join, J.ev_sig, J.ev_msm, J.ev_gather, J.ev_partial, J.ev_h2c,
+                       J.ev_fb,   J.ev_fe,   J.ev_bis, J.ev_own, J.ev_comm,   J.ev_cv,      J.ev_bits};
   for (hipEvent_t e : es)
     if (e) (void)hipEventDestroy(e);
   if (J.h_partial) (void)hipHostFree(J.h_partial);
+  if (J.bits_tab) (void)hipHostFree(J.bits_tab);
   if (J.h_own) (void)hipHostFree(J.h_own);
   for (hipStream_t s : ss)
     if (s) (void)hipStreamDestroy(s);
@@ -533,6 +561,8 @@ void bls_ctx_destroy(bls_ctx* ctx) {
     (void)hipEventDestroy(p.second);
   }
   if (ctx->reg) (void)hipFree(ctx->reg);
+  for (void* p : {(void*)ctx->ctab_idx, (void*)ctx->ctab_offs, (void*)ctx->ctab_sum, (void*)ctx->ctab_stat})
+    if (p) (void)hipFree(p);
   if (ctx->comb) (void)hipFree(ctx->comb);
   if (ctx->force_fb) (void)hipFree(ctx->force_fb);
   if (ctx->pc_stage) (void)hipHostFree(ctx->pc_stage);
@@ -1169,6 +1199,57 @@ int bls_registry_generate(bls_ctx* ctx, uint64_t first_sk, size_t n, uint8_t* ou
 
 uint64_t bls_registry_generation(bls_ctx* ctx) { return ctx ? ctx->reg_gen : 0; }
 
+// ------------------------------------------------------ committee table --
+// The lists and their offsets stay in HBM; one launch of the bits gather over the table itself (every committee a
+// direct item whose list is its members) gives csum[c], and its members_ok output is cstat[c] -- apart from the
+// identity check, so an empty committee or one whose keys cancel is usable (cstat 1) with the identity as its sum.
+int bls_committees_load(bls_ctx* ctx, const uint32_t* idx, const uint64_t* offsets, size_t C) {
+  API_ENTER(ctx);
+  if (!ctx->reg || !ctx->reg_n) {
+    ctx->err = "no registry loaded";
+    return BLS_E_NOREG;
+  }
+  if (!offsets || C >= 0x80000000u) return BLS_E_ARG;
+  for (size_t c = 0; c < C; c++)
+    if (offsets[c + 1] < offsets[c] || offsets[c + 1] - offsets[c] > 0xffffffffull) return BLS_E_ARG;
+  const uint64_t o0 = offsets[0], total = offsets[C] - o0;
+  if (total && !idx) return BLS_E_ARG;
+  HIPCK(hipDeviceSynchronize());  // batches in flight on any job read the old table
+  ctx->ctab_loaded = false;
+  for (void** p : {(void**)&ctx->ctab_idx, (void**)&ctx->ctab_offs, (void**)&ctx->ctab_sum, (void**)&ctx->ctab_stat}) {
+    if (*p) HIPCK(hipFree(*p));
+    *p = nullptr;
+  }
+  HIPCK(hipMalloc(&ctx->ctab_idx, (total ? total : 1) * 4));
+  HIPCK(hipMalloc(&ctx->ctab_offs, (C + 1) * 8));
+  HIPCK(hipMalloc(&ctx->ctab_sum, (C ? C : 1) * sizeof(G1P)));
+  HIPCK(hipMalloc(&ctx->ctab_stat, (C ? C : 1) * sizeof(int)));
+  ctx->ctab_offs_h.resize(C + 1);
+  std::vector<BitsItem> items(C);
+  for (size_t c = 0; c <= C; c++) ctx->ctab_offs_h[c] = offsets[c] - o0;
+  for (size_t c = 0; c < C; c++)
+    items[c] = BitsItem{ctx->ctab_offs_h[c], (uint32_t)(ctx->ctab_offs_h[c + 1] - ctx->ctab_offs_h[c]), BITS_F_SOME};
+  BitsItem* d_items;
+  int* d_st;
+  ctx->j->bits_B = 0;  // the slot's item records become the table's: no batch's work is left to read there
+  SCR(S_BITEM, C, d_items);
+  SCR(S_OK, C, d_st);
+  hipStream_t st = ctx->j->stream;
+  if (total) HIPCK(hipMemcpyAsync(ctx->ctab_idx, idx + o0, total * 4, hipMemcpyHostToDevice, st));
+  HIPCK(hipMemcpyAsync(ctx->ctab_offs, ctx->ctab_offs_h.data(), (C + 1) * 8, hipMemcpyHostToDevice, st));
+  if (C) HIPCK(hipMemcpyAsync(d_items, items.data(), C * sizeof(BitsItem), hipMemcpyHostToDevice, st));
+  LK(launch_fav_gather_bits(st, ctx->ctab_idx, d_items, C, ctx->reg, (uint32_t)ctx->reg_n, nullptr, nullptr, nullptr,
+                            ctx->ctab_sum, d_st, ctx->ctab_stat));
+  HIPCK(hipStreamSynchronize(st));
+  ctx->ctab_gen = ctx->reg_gen;
+  ctx->ctab_loaded = true;
+  return 1;
+}
+
+size_t bls_committees_count(bls_ctx* ctx) {
+  return (ctx && ctx->ctab_loaded) ? ctx->ctab_offs_h.size() - 1 : 0;
+}
+
 int bls_profile_enable(bls_ctx* ctx, int on) {
   API_ENTER(ctx);
   HIPCK(hipStreamSynchronize(ctx->j->stream));
@@ -1214,9 +1295,89 @@ constexpr size_t ACC_SHARED_MIN = 4096;  // items per FAV batch from which k_mil
 // per-message stages (hash_to_G2, G2 lines, f accumulation) run over M + MSM_UPAIRS pairs whose G1 side is the
 // segmented sum of the items' r_i apk_i (bls_g1_segsum.h), and the kernel-form thresholds key on M.  Without a
 // grouping (every existing entry point) the launches are what they always were.
+//
+// bits (nullable): the items are (committees, participation bits) over the context's committee table instead of
+// index lists (d_idx / d_offs unused).  bits_plan has checked the arguments and left the host tables in the job;
+// a pre-stage expands every item into the list its gather adds, and the gather variant of bls_gather_bits.hip
+// writes the same apka / gstat the index gather would have written for the expanded list.  Nothing after them
+// knows the difference.  Without bits the launches are what they always were.
+struct BitsArgs {
+  const uint8_t* d_bits;  // device: the items' bit bytes, item b at bit_offs[b]
+  int mode;
+};
+
+// The host half of a bits batch, before any device call: every committee id names a table entry, item b carries
+// exactly ceil(n_b / 8) bytes (n_b the members of its committees), and the table is the registry's.  Leaves the
+// job-owned copies (committee ids rebased to 0, comm_offs | bit_offs | slot_offs) that fav_prepare uploads.
+static int bits_plan(bls_ctx* ctx, const uint32_t* comm_ids, const uint64_t* comm_offs, const uint64_t* bit_offs,
+                     size_t B, int mode) {
+  if (!ctx->ctab_loaded) {
+    ctx->err = "no committee table loaded (bls_committees_load)";
+    return BLS_E_ARG;
+  }
+  if (ctx->ctab_gen != ctx->reg_gen) {
+    ctx->err = "the committee table is stale: the registry was replaced after bls_committees_load";
+    return BLS_E_ARG;
+  }
+  if (mode != BITS_MODE_AUTO && mode != BITS_MODE_DIRECT && mode != BITS_MODE_COMPLEMENT) {
+    ctx->err = "mode must be 0 (auto), 1 (direct) or 2 (complement)";
+    return BLS_E_ARG;
+  }
+  if (!comm_offs || !bit_offs) return BLS_E_ARG;
+  const size_t C = ctx->ctab_offs_h.size() - 1;
+  const uint64_t c0 = comm_offs[0];
+  for (size_t b = 0; b < B; b++)
+    if (comm_offs[b + 1] < comm_offs[b] || bit_offs[b + 1] < bit_offs[b]) return BLS_E_ARG;
+  const uint64_t ncomm = comm_offs[B] - c0;
+  if (ncomm && !comm_ids) return BLS_E_ARG;
+  Job& J = *ctx->j;
+  std::vector<uint64_t>& n = J.bits_n;
+  n.resize(B);
+  for (size_t b = 0; b < B; b++) {
+    n[b] = 0;
+    for (uint64_t j = comm_offs[b]; j < comm_offs[b + 1]; j++) {
+      const uint32_t c = comm_ids[j];
+      if (c >= C) {
+        ctx->err = "committee id out of range";
+        return BLS_E_ARG;
+      }
+      n[b] += ctx->ctab_offs_h[c + 1] - ctx->ctab_offs_h[c];
+    }
+    if (n[b] > 0xffffffffull || bit_offs[b + 1] - bit_offs[b] != (n[b] + 7) / 8) {
+      ctx->err = "an item needs ceil(n / 8) bytes of bits for the n members of its committees";
+      return BLS_E_ARG;
+    }
+  }
+  // the arguments stand: now the job's tables (an upload still in flight reads the old ones)
+  J.bits_B = 0;
+  if (J.bits_up_pending) {
+    HIPCK(hipEventSynchronize(J.ev_bits));
+    J.bits_up_pending = false;
+  }
+  const size_t bytes = 3 * (B + 1) * 8 + ncomm * 4;
+  if (J.bits_tab_cap < bytes) {
+    if (J.bits_tab) HIPCK(hipHostFree(J.bits_tab));
+    J.bits_tab = nullptr;
+    J.bits_tab_cap = 0;
+    HIPCK(hipHostMalloc((void**)&J.bits_tab, bytes + bytes / 4, hipHostMallocDefault));
+    J.bits_tab_cap = bytes + bytes / 4;
+  }
+  J.bits_tab_bytes = bytes;
+  uint64_t* co = J.bits_tab;
+  uint64_t *bo = co + (B + 1), *so = bo + (B + 1);
+  so[0] = 0;
+  for (size_t b = 0; b < B; b++) so[b + 1] = so[b] + n[b];
+  for (size_t b = 0; b <= B; b++) {
+    co[b] = comm_offs[b] - c0;
+    bo[b] = bit_offs[b];
+  }
+  if (ncomm) memcpy(so + (B + 1), comm_ids + c0, ncomm * 4);
+  return 0;
+}
+
 static int fav_prepare(bls_ctx* ctx, const uint32_t* d_idx, const uint64_t* d_offs, size_t B, const uint8_t* d_msgs,
                        const uint8_t* d_sigs, const uint8_t* seed32, Fp12** out_f, size_t M = 0,
-                       const uint32_t* msg_id = nullptr) {
+                       const uint32_t* msg_id = nullptr, const BitsArgs* bits = nullptr) {
   if (!ctx->reg || !ctx->reg_n) {
     ctx->err = "no registry loaded";
     return BLS_E_NOREG;
@@ -1333,6 +1494,26 @@ static int fav_prepare(bls_ctx* ctx, const uint32_t* d_idx, const uint64_t* d_of
   }
   HIPCK(hipStreamWaitEvent(st2, fork, 0));
   if (!two) HIPCK(hipStreamWaitEvent(st3, fork, 0));
+  uint32_t* d_list = nullptr;
+  uint64_t* d_tab = nullptr;
+  BitsItem* d_bitems = nullptr;
+  if (bits) {
+    // (committees, bits) items, the pre-stage: the job's tables up in one copy, then one wave per item expands it
+    // into its index list at the slot the host computed (the prefix sum of the member counts).  On stream2, in
+    // front of the hash -- whose chain waits for the MSM anyway -- so that the expansion runs beside the signature
+    // decode instead of in front of the gather: a job's latency, which a fixed pipeline depth turns into
+    // throughput, stays what the index form's is.  The gather waits for ev_bits.
+    SCR(S_BTAB, (J.bits_tab_bytes + 7) / 8, d_tab);
+    SCR(S_BLIST, J.bits_tab[3 * (B + 1) - 1], d_list);
+    SCR(S_BITEM, B, d_bitems);
+    HIPCK(hipMemcpyAsync(d_tab, J.bits_tab, J.bits_tab_bytes, hipMemcpyHostToDevice, st2));
+    const uint32_t* d_comm = reinterpret_cast<const uint32_t*>(d_tab + 3 * (B + 1));
+    PROF2(14, st2, launch_bits_expand(st2, B, bits->mode, d_comm, d_tab, bits->d_bits, d_tab + (B + 1),
+                                      d_tab + 2 * (B + 1), ctx->ctab_idx, ctx->ctab_offs, ctx->ctab_stat, d_list,
+                                      d_bitems));
+    HIPCK(hipEventRecord(J.ev_bits, st2));
+    J.bits_up_pending = true;
+  }
   PROF2(2, st2, launch_h2c(st2, NH, d_msgs, nullptr, hcf, H, flag));
   CK(h2c_fallback(ctx, st2, NH, d_msgs, nullptr, flag, H));
   if (shared)
@@ -1350,8 +1531,18 @@ static int fav_prepare(bls_ctx* ctx, const uint32_t* d_idx, const uint64_t* d_of
   // (~790 exclusive SIMD-ms, as much as it saved); cutting the complete kernel's own instructions by 15.8 % (one
   // reduction per output coordinate, bls_fq_g1.h) gained C2 3.1 % (profiles/g1dot_ab.txt).
   const char* gv = getenv("BLS_GATHER");
-  const size_t gw = (gv && !strcmp(gv, "affine")) ? fav_gather_aff_words(B) : 0;
-  if (gw) {
+  const size_t gw = (gv && !strcmp(gv, "affine") && !bits) ? fav_gather_aff_words(B) : 0;
+  if (bits) {
+    // the gather variant sums the expanded lists -- and, for complement items, subtracts them from the committees'
+    // cached sums.  The affine gather has no such form.
+    HIPCK(hipStreamWaitEvent(st, J.ev_bits, 0));
+    PROF(0, launch_fav_gather_bits(st, d_list, d_bitems, B, ctx->reg, (uint32_t)ctx->reg_n,
+                                   reinterpret_cast<const uint32_t*>(d_tab + 3 * (B + 1)), d_tab, ctx->ctab_sum, apka,
+                                   gstat, nullptr));
+    J.bits_B = B;
+    J.bits_items = d_bitems;
+    ctx->work_job = &J;
+  } else if (gw) {
     uint32_t* gscr;
     int* redo;
     SCR(S_GAFF, gw, gscr);
@@ -1588,29 +1779,37 @@ static int host_seed(bls_ctx* ctx, uint8_t seed[32]) {
 
 // One host-buffer FAV batch: copies in, RLC batch check, bisection on failure.
 // msg_id (nullable) / M: msgs32 is a table of M messages and item b signs entry msg_id[b] (fav_prepare)
+// bits / bits_bytes (nullable): a committee-bitfield batch -- idx / offsets unused, bits_plan has run, and the
+// bit bytes go up in the index list's place
 static int fav_batch_host(bls_ctx* ctx, const uint32_t* idx, const uint64_t* offsets, size_t B, const uint8_t* msgs32,
-                          const uint8_t* sigs96, uint8_t* out, size_t M = 0, const uint32_t* msg_id = nullptr) {
+                          const uint8_t* sigs96, uint8_t* out, size_t M = 0, const uint32_t* msg_id = nullptr,
+                          const uint8_t* bits = nullptr, size_t bits_bytes = 0, int mode = 0) {
   if (msg_id) {  // before any device call
     if (!M) return BLS_E_ARG;
     for (size_t b = 0; b < B; b++)
       if (msg_id[b] >= M) return BLS_E_ARG;
   }
   const size_t nmsg = msg_id ? M : B;
-  const uint64_t nidx = offsets[B];
-  if (nidx && !idx) return BLS_E_ARG;
-  if (nidx > 0xffffffffull * 64) return BLS_E_ARG;
-  for (size_t b = 0; b < B; b++)
-    if (offsets[b + 1] < offsets[b]) return BLS_E_ARG;
-  uint32_t* d_idx;
-  uint64_t* d_offs;
-  uint8_t *d_m, *d_s, *d_out;
-  SCR(S_IN0, nidx, d_idx);
-  SCR(S_OFFS, B + 1, d_offs);
+  uint32_t* d_idx = nullptr;
+  uint64_t* d_offs = nullptr;
+  uint8_t *d_m, *d_s, *d_out, *d_bits = nullptr;
+  if (bits) {
+    SCR(S_IN0, bits_bytes, d_bits);
+    CK(h2d(ctx, d_bits, bits, bits_bytes));
+  } else {
+    const uint64_t nidx = offsets[B];
+    if (nidx && !idx) return BLS_E_ARG;
+    if (nidx > 0xffffffffull * 64) return BLS_E_ARG;
+    for (size_t b = 0; b < B; b++)
+      if (offsets[b + 1] < offsets[b]) return BLS_E_ARG;
+    SCR(S_IN0, nidx, d_idx);
+    SCR(S_OFFS, B + 1, d_offs);
+    CK(h2d(ctx, d_idx, idx, nidx * 4));
+    CK(h2d(ctx, d_offs, offsets, (B + 1) * 8));
+  }
   SCR(S_IN1, 32 * nmsg, d_m);
   SCR(S_IN2, 96 * B, d_s);
   SCR(S_IN3, B, d_out);
-  CK(h2d(ctx, d_idx, idx, nidx * 4));
-  CK(h2d(ctx, d_offs, offsets, (B + 1) * 8));
   CK(h2d(ctx, d_m, msgs32, 32 * nmsg));
   CK(h2d(ctx, d_s, sigs96, 96 * B));
   uint8_t seed[32];
@@ -1619,7 +1818,8 @@ static int fav_batch_host(bls_ctx* ctx, const uint32_t* idx, const uint64_t* off
   // (an earlier call's, recorded before these copies; the hash would read the previous contents of S_IN1)
   ctx->j->bis_pending = false;
   Fp12* f;
-  CK(fav_prepare(ctx, d_idx, d_offs, B, d_m, d_s, seed, &f, M, msg_id));
+  const BitsArgs ba{d_bits, mode};
+  CK(fav_prepare(ctx, d_idx, d_offs, B, d_m, d_s, seed, &f, M, msg_id, bits ? &ba : nullptr));
   int ok = run_final_check(ctx, f);
   if (ok < 0) return ok;
   CK(fav_finish(ctx, ok, true, d_out));
@@ -1665,6 +1865,41 @@ int bls_verify_batch_indexed_shared(bls_ctx* ctx, const uint32_t* idx, size_t B,
   std::vector<uint64_t> offs(B + 1);
   for (size_t i = 0; i <= B; i++) offs[i] = i;
   return fav_batch_host(ctx, idx, offs.data(), B, msgs32, sigs96, out, M, msg_id);
+}
+
+int bls_fav_batch_committee_bits(bls_ctx* ctx, const uint32_t* comm_ids, const uint64_t* comm_offs,
+                                 const uint8_t* bits, const uint64_t* bit_offs, size_t B, const uint8_t* msgs32,
+                                 size_t M, const uint32_t* msg_id, const uint8_t* sigs96, int mode, uint8_t* out) {
+  API_ENTER(ctx);
+  if ((!comm_offs || !bit_offs || !msgs32 || !sigs96 || !out) && B) return BLS_E_ARG;
+  if (!B) return 1;
+  CK(bits_plan(ctx, comm_ids, comm_offs, bit_offs, B, mode));
+  if (bit_offs[B] && !bits) return BLS_E_ARG;
+  static const uint8_t none = 0;  // a batch whose items all have no member still takes the bits route
+  return fav_batch_host(ctx, nullptr, nullptr, B, msgs32, sigs96, out, M, msg_id, bits ? bits : &none,
+                        (size_t)bit_offs[B], mode);
+}
+
+// The item records say what the gather added: read back and summed here, so the batch itself pays nothing for it.
+int bls_last_gather_work(bls_ctx* ctx, uint64_t* points_added, uint64_t* complement_items) {
+  API_ENTER(ctx);
+  uint64_t pts = 0, ncompl = 0;
+  if (ctx->work_job && ctx->work_job->bits_B) {
+    Job& J = *ctx->work_job;
+    std::vector<BitsItem> it(J.bits_B);
+    HIPCK(hipMemcpyAsync(it.data(), J.bits_items, J.bits_B * sizeof(BitsItem), hipMemcpyDeviceToHost, J.stream));
+    HIPCK(hipStreamSynchronize(J.stream));
+    for (size_t b = 0; b < J.bits_B; b++) {
+      pts += it[b].len;
+      if (it[b].flags & BITS_F_COMPLEMENT) {
+        pts += J.bits_tab[b + 1] - J.bits_tab[b];  // its committees' sums
+        ncompl++;
+      }
+    }
+  }
+  if (points_added) *points_added = pts;
+  if (complement_items) *complement_items = ncompl;
+  return 0;
 }
 
 int bls_last_batch_work(bls_ctx* ctx, uint64_t* hashes, uint64_t* miller_pairs) {
@@ -2277,13 +2512,13 @@ static int enqueue_comm_check(bls_ctx* ctx) {
 // the rank still joins every all-gather and its peers never wait for it.
 static int job_submit(bls_ctx* ctx, const uint32_t* d_idx, const uint64_t* d_offsets, size_t B, const uint8_t* d_msgs32,
                       const uint8_t* d_sigs96, const uint8_t* seed32, bool exchange, size_t M = 0,
-                      const uint32_t* msg_id = nullptr) {
+                      const uint32_t* msg_id = nullptr, const BitsArgs* bits = nullptr) {
   exchange = exchange && ctx->comm;
-  if (!seed32 || (B && (!d_offsets || !d_msgs32 || !d_sigs96)) || (!B && !exchange)) return BLS_E_ARG;
+  if (!seed32 || (B && ((!d_offsets && !bits) || !d_msgs32 || !d_sigs96)) || (!B && !exchange)) return BLS_E_ARG;
   Job& J = *ctx->j;
   Fp12* f;
   if (B) {
-    CK(fav_prepare(ctx, d_idx, d_offsets, B, d_msgs32, d_sigs96, seed32, &f, M, msg_id));
+    CK(fav_prepare(ctx, d_idx, d_offsets, B, d_msgs32, d_sigs96, seed32, &f, M, msg_id, bits));
   } else {
     SCR(S_FPART, 1, f);
     hipLaunchKernelGGL(k_fp12_set_one, dim3(1), dim3(64), 0, J.stream, f);
@@ -2435,6 +2670,24 @@ int bls_fav_job_submit_shared_dev(bls_ctx* ctx, int job, const uint32_t* d_idx, 
   int r = BLS_E_ARG;
   if (!B || msg_id)  // an empty shard has no ids; fav_prepare refuses M == 0 and ids >= M before any device call
     r = job_submit(ctx, d_idx, d_offsets, B, d_msgs32, d_sigs96, seed32, true, M, B ? msg_id : nullptr);
+  if (r < 0 && ctx->comm) comm_fail_abort(ctx);
+  return r;
+}
+
+// msg_id == nullptr: one message per item; else the shared-message form over a table of M.  An empty shard
+// (B == 0, the device exchange only) takes no table and no bits.
+int bls_fav_job_submit_bits_dev(bls_ctx* ctx, int job, const uint32_t* comm_ids, const uint64_t* comm_offs,
+                                const uint8_t* d_bits, const uint64_t* bit_offs, size_t B, const uint8_t* d_msgs32,
+                                size_t M, const uint32_t* msg_id, const uint8_t* d_sigs96, int mode,
+                                const uint8_t* seed32) {
+  JOB_ENTER(ctx, job);
+  int r = B ? bits_plan(ctx, comm_ids, comm_offs, bit_offs, B, mode) : 0;
+  if (r == 0 && B && bit_offs[B] && !d_bits) r = BLS_E_ARG;
+  if (r == 0) {
+    const BitsArgs ba{d_bits, mode};
+    r = job_submit(ctx, nullptr, nullptr, B, d_msgs32, d_sigs96, seed32, true, msg_id ? M : 0, B ? msg_id : nullptr,
+                   B ? &ba : nullptr);
+  }
   if (r < 0 && ctx->comm) comm_fail_abort(ctx);
   return r;
 }

@@ -23,6 +23,20 @@ hipError_t launch_fav_gather_aff(hipStream_t st, const uint32_t* idx, const uint
                                  const RegKey* reg, uint32_t reg_n, G1P* apk, int* status, uint32_t* scr, int* redo);
 hipError_t launch_fav_gather_redo(hipStream_t st, const uint32_t* idx, const uint64_t* offs, size_t B,
                                   const RegKey* reg, uint32_t reg_n, G1P* apk, int* status, const int* redo);
+// committee-bitfield batches (bls_gather_bits.hip, bls_g1_bits.h): one wave per item expands (committees, bits) into
+// the list of registry indices the gather adds -- the participants, or for a complement item the non-participants --
+// at list[slot_offs[b] ..), with the item's record (length, form, malformed);
+// the gather variant then sums each list and, for complement items, subtracts it from the committees' sums csum.
+// members_ok (nullable): 1 iff every listed key was in range and valid (the committee table's cstat)
+struct BitsItem;
+hipError_t launch_bits_expand(hipStream_t st, size_t B, int mode, const uint32_t* comm_ids, const uint64_t* comm_offs,
+                              const uint8_t* bits, const uint64_t* bit_offs, const uint64_t* slot_offs,
+                              const uint32_t* tab_idx, const uint64_t* tab_offs, const int* cstat, uint32_t* list,
+                              BitsItem* items);
+hipError_t launch_fav_gather_bits(hipStream_t st, const uint32_t* list, const BitsItem* items, size_t B,
+                                  const RegKey* reg, uint32_t reg_n, const uint32_t* comm_ids,
+                                  const uint64_t* comm_offs, const G1P* csum, G1P* apk, int* status,
+                                  int* members_ok);
 // registry entries from k_key_validate output (+ the host validity mask)
 hipError_t launch_reg_pack(hipStream_t st, const G1A* a, const int* ok, size_t n, RegKey* reg, uint8_t* valid);
 hipError_t launch_av_items(hipStream_t st, size_t B, const uint64_t* io, const int* pk_ok, const int* sig_ok, const G2A* sig, const uint64_t* rsc, int* status, G1A* P2, G2A* Q2);

@@ -167,6 +167,47 @@ int bls_verify_batch_indexed_shared(bls_ctx* ctx, const uint32_t* idx, size_t B,
  * batch reports B and B + 64, a shared one M and M + 64.  Returns 0. */
 int bls_last_batch_work(bls_ctx* ctx, uint64_t* hashes, uint64_t* miller_pairs);
 
+/* Committee table: C committees as registry index lists, committee c =
+ * idx[offsets[c] .. offsets[c+1]) (offsets has C+1 entries).  The lists stay
+ * in HBM, replacing any earlier table, and one launch computes each
+ * committee's projective key sum csum[c] and cstat[c] = 1 iff every member
+ * index is below the registry size and marked valid.  An empty committee and
+ * one whose sum is the identity are allowed (cstat 1).  The table belongs to
+ * the registry generation it was loaded on: after bls_registry_load or
+ * bls_registry_generate it is stale and the bits calls below return
+ * BLS_E_ARG; bls_registry_append keeps it (a member that was out of range at
+ * load time keeps cstat 0).  Returns 1 or BLS_E_*. */
+int bls_committees_load(bls_ctx* ctx, const uint32_t* idx, const uint64_t* offsets, size_t C);
+size_t bls_committees_count(bls_ctx* ctx);
+
+/* B FastAggregateVerify calls whose signers are given as an attestation gives
+ * them (get_attesting_indices): item b names the committees
+ * comm_ids[comm_offs[b] .. comm_offs[b+1]) of the table and carries one bit
+ * per member of their concatenation, in the bytes
+ * bits[bit_offs[b] .. bit_offs[b+1]); bit k = (byte[k/8] >> (k%8)) & 1, the
+ * SSZ bit order without the Bitlist delimiter.  With n_b the member count of
+ * the item's committees, out[b] is what bls_fav_batch_indexed (msg_id NULL:
+ * one message per item, M ignored) or bls_fav_batch_indexed_shared (msg_id:
+ * a table of M messages) returns for the expanded index list -- the members
+ * whose bit is 1, in order -- for every table, whatever it holds.
+ * BLS_E_ARG before any device call: a committee id >= C, a byte count other
+ * than ceil(n_b / 8), a bad msg_id, no or a stale table.  Verdict 0, decided
+ * on the device: a padding bit set in the last byte; n_b == 0 or no bit set.
+ * mode 0 (auto): an item's key is the committees' sums minus the
+ * non-participants' keys iff every committee of the item has cstat 1 and
+ * that adds fewer points, (n_b - p) + ncomm < p with p the bits set;
+ * mode 1: always the participants' sum; mode 2: the complement wherever
+ * cstat allows it (an item with no bit set has no work in any mode).  Modes
+ * 1 and 2 are for tests and measurements.  Returns 1 or BLS_E_*. */
+int bls_fav_batch_committee_bits(bls_ctx* ctx, const uint32_t* comm_ids, const uint64_t* comm_offs,
+                                 const uint8_t* bits, const uint64_t* bit_offs, size_t B, const uint8_t* msgs32,
+                                 size_t M, const uint32_t* msg_id, const uint8_t* sigs96, int mode, uint8_t* out);
+
+/* The last bits batch prepared on this context (either entry point): points
+ * its gather added -- keys, plus committee sums of complement items -- and
+ * the number of complement items.  Waits for that batch's gather.  Returns 0. */
+int bls_last_gather_work(bls_ctx* ctx, uint64_t* points_added, uint64_t* complement_items);
+
 /* B AggregateVerify calls <- E/utils/bls.py:154-164 (one call per item).
  * Item b owns the pairs item_offs[b] .. item_offs[b+1] (item_offs has B+1
  * entries, total = item_offs[B]): pubkeys pks48[48 t ..], messages
@@ -307,6 +348,16 @@ int bls_fav_job_submit_dev(bls_ctx* ctx, int job, const uint32_t* d_idx, const u
 int bls_fav_job_submit_shared_dev(bls_ctx* ctx, int job, const uint32_t* d_idx, const uint64_t* d_offsets, size_t B,
                                   const uint8_t* d_msgs32, size_t M, const uint32_t* msg_id,
                                   const uint8_t* d_sigs96, const uint8_t* seed32);
+/* The committee-bitfield form of submit (bls_fav_batch_committee_bits): the
+ * bit bytes d_bits, the messages (B of them, or with msg_id a table of M) and
+ * d_sigs96 are device resident; comm_ids, comm_offs, bit_offs and msg_id are
+ * HOST arrays, checked before any device call and uploaded from job-owned
+ * copies that live until the job is finished.  The calls around it are
+ * unchanged. */
+int bls_fav_job_submit_bits_dev(bls_ctx* ctx, int job, const uint32_t* comm_ids, const uint64_t* comm_offs,
+                                const uint8_t* d_bits, const uint64_t* bit_offs, size_t B, const uint8_t* d_msgs32,
+                                size_t M, const uint32_t* msg_id, const uint8_t* d_sigs96, int mode,
+                                const uint8_t* seed32);
 int bls_fav_job_partial(bls_ctx* ctx, int job, uint8_t* partial576);
 int bls_fav_job_check(bls_ctx* ctx, int job, const uint8_t* partials576, size_t n);
 /* check_own: the final exponentiation of the job's own product alone, which
