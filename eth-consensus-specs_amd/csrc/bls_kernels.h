@@ -16,7 +16,7 @@ hipError_t launch_hash_many(hipStream_t st, const uint8_t* msgs, const uint64_t*
 hipError_t launch_sign_many(hipStream_t st, const uint8_t* sks, const uint8_t* msgs, const uint64_t* offs, size_t n, uint8_t* out, int* ok);
 hipError_t launch_sk_to_pk_many(hipStream_t st, const uint8_t* sks, size_t n, uint8_t* out, int* ok);
 hipError_t launch_fav_gather(hipStream_t st, const uint32_t* idx, const uint64_t* offs, size_t B, const RegKey* reg, uint32_t reg_n, G1P* apk, int* status);
-// the affine gather (bls_gather_aff.hip) for batches of >= 1,024 aggregates: scratch of fav_gather_aff_words(B) u32,
+// the affine gather (bls_gather_aff.hip) for batches of >= 4,096 aggregates: scratch of fav_gather_aff_words(B) u32,
 // redo[B] (1 = recompute with launch_fav_gather_redo, the complete-formula kernel on the flagged aggregates only)
 size_t fav_gather_aff_words(size_t B);
 hipError_t launch_fav_gather_aff(hipStream_t st, const uint32_t* idx, const uint64_t* offs, size_t B,
@@ -69,7 +69,7 @@ hipError_t launch_h2c(hipStream_t st, size_t B, const uint8_t* msgs32, const int
 hipError_t launch_h2c_msgs(hipStream_t st, size_t B, const uint8_t* msgs, const uint64_t* offs, Fd* hf, G2A* H,
                            int* flag);
 // exceptional h2c items (flag set: an isogeny denominator vanished) recomputed by one workgroup; offs == nullptr
-// for 32-byte messages.  Not part of launch_h2c / launch_h2c_msgs: the caller picks its stream (bls_capi.hip).
+// for 32-byte messages.  Not part of launch_h2c / launch_h2c_msgs: the caller picks its stream (bls_capi_ctx.hip).
 hipError_t launch_h2c_fallback(hipStream_t st, size_t B, const uint8_t* msgs, const uint64_t* offs, const int* flag,
                                G2A* H);
 hipError_t launch_sig_decode(hipStream_t st, size_t B, const uint8_t* msgs32, const uint8_t* sigs96, const uint8_t* seed32, G2A* sig, uint64_t* rsc, int* dstat);

@@ -171,6 +171,52 @@ def test_multi_pairing_and_gt(shim, setup):
     assert shim.pairing_check([[P_minus_y, shim.neg(shim.G2())], [shim.multiply(shim.G1(), 2), X_minus_z]]) is False
 
 
+def test_pairing_entry_points_on_cancelling_pairs(shim):
+    """bls_pairing_check, bls_pairing_check_ex with and without the subgroup checks, and bls_multi_pairing (both
+    flags) share one staging / decode / Miller body: two pairs that cancel, two that do not, and a point outside
+    G1 (rejected exactly where the subgroup checks run), each against the oracle."""
+    import ctypes
+
+    from bls_mi355x import _native, batch
+    from bls_mi355x.curve import GT_ONE
+
+    c = _native.context()
+    P, Q = O.g1_mul(O.G1_GEN, 77), O.g2_mul(O.G2_GEN, 1234567)
+    cancel = [(P, Q), (O.g1_neg(P), Q)]
+    twice = [(P, Q), (P, Q)]
+    assert O.pairing_product_is_one(cancel) and not O.pairing_product_is_one(twice)
+    ns = _non_subgroup_g1()
+    outside = [(ns, Q), (O.g1_neg(P), Q)]
+
+    def enc(pairs):
+        return b"".join(O.g1_compress(p) for p, _ in pairs), b"".join(O.g2_compress(q) for _, q in pairs)
+
+    def multi(pairs, flag):
+        out = ctypes.create_string_buffer(576)
+        rc = c.check(c.lib.bls_multi_pairing(c.h, *enc(pairs), len(pairs), flag, out))
+        return rc, out.raw
+
+    def gt(pairs):
+        f = O.F12_ONE
+        for p, q in pairs:
+            f = O.f12_mul(f, O.miller_loop(p, q))
+        return _gt_bytes(O.final_exponentiation(f))
+
+    for pairs in (cancel, twice):
+        want = O.pairing_product_is_one(pairs)
+        assert batch.pairing_check([(O.g1_compress(p), O.g2_compress(q)) for p, q in pairs], ctx=c) is want
+        for flag in (0, 1):
+            assert c.check(c.lib.bls_pairing_check_ex(c.h, *enc(pairs), 2, flag)) == int(want)
+            assert multi(pairs, flag) == (1, gt(pairs))
+    assert multi(cancel, 0)[1] == GT_ONE
+    # outside G1: 0 from every entry point that checks the subgroup; unchecked, the oracle's value
+    assert batch.pairing_check([(O.g1_compress(p), O.g2_compress(q)) for p, q in outside], ctx=c) is False
+    assert c.check(c.lib.bls_pairing_check_ex(c.h, *enc(outside), 2, 1)) == 0
+    assert multi(outside, 1)[0] == 0
+    assert multi(outside, 0) == (1, gt(outside))
+    assert c.check(c.lib.bls_pairing_check_ex(c.h, *enc(outside), 2, 0)) == int(O.pairing_product_is_one(outside))
+
+
 def test_sync_aggregate_complement(shim):
     """process_sync_aggregate (specs/altair/beacon-chain.md:582-596): the participants' aggregate key as the
     committee aggregate minus the non-participants' aggregate, then FastAggregateVerify with it."""
