@@ -58,6 +58,7 @@ inline void fq_check_dot2(const Fq& x, const Fq& y, const Fq& u, const Fq& v) {
   assert(fq_check_top(x) * fq_check_top(y) + fq_check_top(u) * fq_check_top(v) < 13.0 * __builtin_ldexp(1.0, 29));
 }
 #define FQ_CHECK_DOT2(x, y, u, v) fq_check_dot2(x, y, u, v)
+#define FQ_CHECK_DOT6(o) fq_check_dot6(o)
 #define FQ_CHECK_COL(acc128) assert((acc128) < ((unsigned __int128)1 << 64))
 #define FQ_CHECK_SUB(b, K)                                        \
   do {                                                            \
@@ -66,6 +67,7 @@ inline void fq_check_dot2(const Fq& x, const Fq& y, const Fq& u, const Fq& v) {
 #else
 #define FQ_CHECK_MUL(x, y) ((void)0)
 #define FQ_CHECK_DOT2(x, y, u, v) ((void)0)
+#define FQ_CHECK_DOT6(o) ((void)0)
 #define FQ_CHECK_COL(acc128) ((void)0)
 #define FQ_CHECK_SUB(b, K) ((void)0)
 #endif
@@ -228,6 +230,88 @@ BLS_HD Fq fq_mul_dot2(const Fq& x, const Fq& y, const Fq& u, const Fq& v) {
     acc >>= 29;
   }
   r.d[13] = (uint32_t)acc;
+  return r;
+}
+
+// Montgomery (x0 y0 + ... + x5 y5) / 2^406 with ONE reduction: the product-scanning loop of fq_mul_dot2 with the
+// column sum split over TWO 64-bit accumulators.  A takes the digit products of terms 0..2 and the 14 reduction
+// products, B those of terms 3..5, so a column holds at most 56 resp. 42 terms (42 + 14 + carry resp. 42 + carry;
+// bls_fqb.h columns_fit6 proves the fit for the operands' digit bounds).  Per column B's low 29 bits are added to A
+// (one more term below 2^29), A then gives the reduction digit or the output digit exactly as fq_mul_dot2's single
+// accumulator does, and both shift down by 29.  N form, value < 2p when the sum of the products is below p R.  The columns are
+// template instances, not an unrolled loop: every index is a constant whatever the unroller's size limits are.
+struct FqDot6 {
+  const Fq &x0, &y0, &x1, &y1, &x2, &y2, &x3, &y3, &x4, &y4, &x5, &y5;
+};
+#ifdef BLS_FQ_CHECK
+// sum x_t y_t < p R, against p / 2^348 = 13.0020898... * 2^29 rounded down in its sixth decimal
+inline void fq_check_dot6(const FqDot6& o) {
+  assert(fq_check_top(o.x0) * fq_check_top(o.y0) + fq_check_top(o.x1) * fq_check_top(o.y1) +
+             fq_check_top(o.x2) * fq_check_top(o.y2) + fq_check_top(o.x3) * fq_check_top(o.y3) +
+             fq_check_top(o.x4) * fq_check_top(o.y4) + fq_check_top(o.x5) * fq_check_top(o.y5) <
+         13.00208 * __builtin_ldexp(1.0, 29));
+}
+#endif
+template <int K>
+BLS_HD void fq_dot6_cols(const FqDot6& o, uint32_t (&m)[14], Fq& r, uint64_t& A, uint64_t& B) {
+  if constexpr (K < 27) {
+    constexpr int LO = K > 13 ? K - 13 : 0, HI = K < 13 ? K : 13, HR = K - 1 < 13 ? K - 1 : 13;
+#ifdef BLS_FQ_CHECK
+    unsigned __int128 ca = A, cb = B;
+#endif
+#pragma unroll
+    for (int i = LO; i <= HI; i++) {
+      const int j = K - i;
+      A += (uint64_t)o.x0.d[i] * o.y0.d[j];
+      A += (uint64_t)o.x1.d[i] * o.y1.d[j];
+      A += (uint64_t)o.x2.d[i] * o.y2.d[j];
+      B += (uint64_t)o.x3.d[i] * o.y3.d[j];
+      B += (uint64_t)o.x4.d[i] * o.y4.d[j];
+      B += (uint64_t)o.x5.d[i] * o.y5.d[j];
+#ifdef BLS_FQ_CHECK
+      ca += (unsigned __int128)o.x0.d[i] * o.y0.d[j] + (unsigned __int128)o.x1.d[i] * o.y1.d[j] +
+            (unsigned __int128)o.x2.d[i] * o.y2.d[j];
+      cb += (unsigned __int128)o.x3.d[i] * o.y3.d[j] + (unsigned __int128)o.x4.d[i] * o.y4.d[j] +
+            (unsigned __int128)o.x5.d[i] * o.y5.d[j];
+#endif
+    }
+#pragma unroll
+    for (int i = LO; i <= HR; i++) {
+      A += (uint64_t)m[i] * P29[K - i];
+#ifdef BLS_FQ_CHECK
+      ca += (unsigned __int128)m[i] * P29[K - i];
+#endif
+    }
+    const uint32_t bl = (uint32_t)B & Q29_MASK;  // B's low digit joins A: the column's low 29 bits are then A's
+    A += bl;
+#ifdef BLS_FQ_CHECK
+    ca += bl;
+#endif
+    if constexpr (K < 14) {
+      m[K] = ((uint32_t)A * P29_NINV) & Q29_MASK;
+      A += (uint64_t)m[K] * P29[0];
+#ifdef BLS_FQ_CHECK
+      ca += (unsigned __int128)m[K] * P29[0];
+#endif
+    } else {
+      r.d[K - 14] = (uint32_t)A & Q29_MASK;
+    }
+    FQ_CHECK_COL(ca);
+    FQ_CHECK_COL(cb);
+    A >>= 29;
+    B >>= 29;
+    fq_dot6_cols<K + 1>(o, m, r, A, B);
+  }
+}
+BLS_HD Fq fq_mul_dot6(const Fq& x0, const Fq& y0, const Fq& x1, const Fq& y1, const Fq& x2, const Fq& y2, const Fq& x3,
+                      const Fq& y3, const Fq& x4, const Fq& y4, const Fq& x5, const Fq& y5) {
+  const FqDot6 o{x0, y0, x1, y1, x2, y2, x3, y3, x4, y4, x5, y5};
+  FQ_CHECK_DOT6(o);
+  uint32_t m[14];
+  Fq r;
+  uint64_t A = 0, B = 0;
+  fq_dot6_cols<0>(o, m, r, A, B);
+  r.d[13] = (uint32_t)A + (uint32_t)B;
   return r;
 }
 

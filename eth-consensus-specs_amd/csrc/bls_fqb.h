@@ -14,6 +14,9 @@
 //                  column -- digit products, reduction products m_i p_j and
 //                  the 2^35 carry -- stays below 2^64 for these digit bounds;
 //                  result FqB<2, 2^29 - 1> (N form)
+//   dot2 / dot6    sums of two / six products with one reduction: the same
+//                  two static_asserts on the sum of V_x V_y and on the columns
+//                  (dot6: of each of its two accumulators, columns_fit6)
 //   relax<V, D>    widening to a declared bound (static_assert)
 // Loop-carried state is declared at a fixed bound and every step's result is
 // relaxed to it, so a loop compiles only if its bounds close (an induction
@@ -58,6 +61,26 @@ constexpr bool columns_fit2(uint64_t dx, uint64_t tx, uint64_t dy, uint64_t ty, 
       s += (unsigned __int128)MASK * P29[j];
     }
     if (s >= ((unsigned __int128)1 << 64)) return false;
+  }
+  return true;
+}
+
+// the same for the two accumulators of fq_mul_dot6: A holds the digit products of terms 0..2, the reduction products
+// and, with its carry (< 2^35), B's low 29 bits: together < 2^36; B those of terms 3..5 and its carry (< 2^35)
+struct Dot6Bounds {
+  uint64_t dx[6], tx[6], dy[6], ty[6];  // digits 0..12 / digit 13 of x_t and y_t
+};
+constexpr bool columns_fit6(const Dot6Bounds& b) {
+  for (int k = 0; k < 27; ++k) {
+    unsigned __int128 sa = (unsigned __int128)1 << 36, sb = (unsigned __int128)1 << 35;
+    for (int i = 0; i < 14; ++i) {
+      const int j = k - i;
+      if (j < 0 || j > 13) continue;
+      for (int t = 0; t < 6; ++t)
+        (t < 3 ? sa : sb) += (unsigned __int128)(i == 13 ? b.tx[t] : b.dx[t]) * (j == 13 ? b.ty[t] : b.dy[t]);
+      sa += (unsigned __int128)MASK * P29[j];
+    }
+    if (sa >= ((unsigned __int128)1 << 64) || sb >= ((unsigned __int128)1 << 64)) return false;
   }
   return true;
 }
@@ -167,6 +190,29 @@ BLS_HD FqN dot2(const FqB<V1, D1>& a, const FqB<V2, D2>& b, const FqB<V3, D3>& c
                                          fqb_detail::top(V4)),
                 "dot product column exceeds 64 bits");
   return {fq_mul_dot2(a.x, b.x, c.x, d.x)};
+}
+// Montgomery (x0 y0 + ... + x5 y5): one reduction for six products (fq_mul_dot6; terms 0..2 share its first
+// accumulator with the reduction products, terms 3..5 have the second)
+template <class X0, class Y0, class X1, class Y1, class X2, class Y2, class X3, class Y3, class X4, class Y4, class X5,
+          class Y5>
+constexpr bool dot6_fits() {
+  using fqb_detail::top;
+  return fqb_detail::columns_fit6(
+      {{X0::dig, X1::dig, X2::dig, X3::dig, X4::dig, X5::dig},
+       {top(X0::val), top(X1::val), top(X2::val), top(X3::val), top(X4::val), top(X5::val)},
+       {Y0::dig, Y1::dig, Y2::dig, Y3::dig, Y4::dig, Y5::dig},
+       {top(Y0::val), top(Y1::val), top(Y2::val), top(Y3::val), top(Y4::val), top(Y5::val)}});
+}
+template <class X0, class Y0, class X1, class Y1, class X2, class Y2, class X3, class Y3, class X4, class Y4, class X5,
+          class Y5>
+BLS_HD FqN dot6(const X0& x0, const Y0& y0, const X1& x1, const Y1& y1, const X2& x2, const Y2& y2, const X3& x3,
+                const Y3& y3, const X4& x4, const Y4& y4, const X5& x5, const Y5& y5) {
+  static_assert(X0::val * Y0::val + X1::val * Y1::val + X2::val * Y2::val + X3::val * Y3::val + X4::val * Y4::val +
+                        X5::val * Y5::val <=
+                    fqb_detail::R_OVER_P,
+                "dot product operand values exceed p R");
+  static_assert(dot6_fits<X0, Y0, X1, Y1, X2, Y2, X3, Y3, X4, Y4, X5, Y5>(), "dot product column exceeds 64 bits");
+  return {fq_mul_dot6(x0.x, y0.x, x1.x, y1.x, x2.x, y2.x, x3.x, y3.x, x4.x, y4.x, x5.x, y5.x)};
 }
 // -b as K - b digit-wise (K = c p covering b's digits, as in a - b)
 template <uint64_t V, uint64_t D>

@@ -3,6 +3,7 @@
 // bound-typed redundant digit form (bls_fqb.h).
 #include <type_traits>
 
+#include "bls_acc_dot.h"
 #include "bls_fqb.h"
 #include "bls_kernels.h"
 #include "bls_miller_lines.h"
@@ -12,9 +13,10 @@ namespace bls {
 
 namespace {
 
-// loop-carried bound of the digit-form f halves: value < ML_QF_V p, digits <= ML_QF_D (every step's output is
-// relaxed to it at compile time: qq_sqr ends below 211 p, qq_line below ML_QF_V p)
-constexpr uint64_t ML_QF_V = 256, ML_QF_D = 0x20000000ull + 64;
+// loop-carried bound of f's halves in the kernels that keep the Karatsuba steps (k_miller_acc4l, k_miller_acc8): value
+// < ML_QK_V p, digits <= ML_QK_D (every step's output is relaxed to it at compile time).  k_miller_acc4q and
+// k_miller_fused carry ML_QF_V / ML_QF_D of bls_acc_dot.h.
+constexpr uint64_t ML_QK_V = 256, ML_QK_D = 0x20000000ull + 64;
 
 // The Fp2 products of each Fp6 product run one after another (sched_barrier): letting the scheduler
 // interleave them held too many products live and spilled (the packed-form kernel measured 5.0 ms per
@@ -42,16 +44,24 @@ constexpr int BQ0 = 0xA0, BQ1 = 0xF5, BH0 = 0x44, BH1 = 0xEE;  // quad_perm [0,0
 //
 // Lane 4k + 2h + q: h selects the half of f it owns (h = 0: a = f.c0, h = 1:
 // b = f.c1, f = a + b w with w^2 = v; the two q lanes of one h hold the same half),
-// q selects which Fp2 products of each Fp6 product it forms:
-//   full Fp6 product   q = 0: t_k = X_k Y_k;  q = 1: the three Karatsuba cross
-//                      products -- three Fp2 products per lane instead of six
-//   line product       q = 0: a_0 l0, a_1 l2, a_2 l2, a_2 l0;  q = 1:
-//                      (a_0 + a_1)(l0 + l2), o_2 l3, o_0 l3, o_1 l3  (o: the
-//                      other half) -- four instead of eight
+// q selects the Fp component of every output coefficient it forms (q = 0: the
+// real part, q = 1: the imaginary part; bls_acc_dot.h):
+//   squaring           the Fp6 product X Y of its half ((a + b)(a + v b) on
+//                      h = 0, a b on h = 1) as schoolbook sums of three Fp2
+//                      products per coefficient: three dot6 per lane, one
+//                      Montgomery reduction each (18 digit products, 3
+//                      reductions; the Karatsuba split it replaces: 12 and 6)
+//   line product       own (l0, l2, 0) + X (0, l3, 0) with X the other half
+//                      (times v on h = 0): three Fp2 products per coefficient
+//                      again, three dot6 per lane (18 digit products, 3
+//                      reductions; before: 16 and 8)
 //   line P factors     lane (h, q) forms component q of its Fp2 x Fp product
-// followed by one DPP exchange (quad_perm [1,0,3,2] between q lanes, [2,3,0,1]
-// between h lanes); both q lanes then hold the same combined result, so the
-// instruction stream is uniform and every lane-dependent choice is a select.
+// The line operands are prepared per lane as (y_q, +-y_(1-q)) and f's digits
+// enter every product as they are, so the instruction stream is uniform; the
+// two q lanes' components are put together by two quad broadcasts per
+// coefficient (quad_perm [0,0,2,2] / [1,1,3,3]), the other half comes over
+// quad_perm [2,3,0,1].  (k_miller_acc4l and k_miller_acc8 keep the Karatsuba
+// split over q or j: qq6mul, q4_6mul, q8_line.)
 // With G = 2 the pairs (2k, 2k+1) share one f: one squaring per step for two
 // Miller loops (f^2 l_A l_B), the multi-pairing form of SURVEY.md §8(d)'s
 // shared-squaring model.  The output is one Fp12 per group; the batch product
@@ -124,35 +134,38 @@ __device__ __forceinline__ auto qq6mul(const Fq6B<VX, DX>& X, const Fq6B<VY, DY>
   return fq6b(c0, c1, c2);
 }
 
-// one Fp12 squaring on the (h, q) lanes, as q_sqr
-template <uint64_t V, uint64_t D>
-__device__ __forceinline__ auto qq_sqr(const Fq6B<V, D>& own, bool h, bool q) {
-  const auto o = dh6(own);  // the other half: b on h = 0, a on h = 1
-  const auto X = norm(sel(h, o, own + o));
-  const auto Y = norm(sel(h, own, own + f6v(o)));
-  const auto P = qq6mul(X, Y, q);
-  const auto t = bc6<BH1>(P);  // a b (the h = 1 lanes' product)
-  return norm(sel(h, P + P, (P - t) - f6v(t)));
+// the exchanges of bls_acc_dot.h's lane functions as quad DPP moves
+struct DppEx {
+  template <int A, int B, uint64_t V, uint64_t D>
+  __device__ __forceinline__ Fq2B<V, D> other(const Fq6B<V, D>& own, bool h) const {
+    return dh2(sel(h, accdot::coef<A>(own), accdot::coef<B>(own)));
+  }
+  template <uint64_t V, uint64_t D>
+  __device__ __forceinline__ Fq6B<V, D> half(const Fq6B<V, D>& own) const {
+    return dh6(own);
+  }
+};
+// both q lanes' components of three coefficients, reassembled on both
+__device__ __forceinline__ accdot::N6 join_q(const FqN (&r)[3]) {
+  return {{bc<BQ0>(r[0]), bc<BQ1>(r[0])}, {bc<BQ0>(r[1]), bc<BQ1>(r[1])}, {bc<BQ0>(r[2]), bc<BQ1>(r[2])}};
 }
 
-// own *= line, as q_line
+// one Fp12 squaring on the (h, q) lanes: three dot6 per lane (accdot::sqr_lane), then a b from the h = 1 lanes
+template <uint64_t V, uint64_t D>
+__device__ __forceinline__ auto qq_sqr(const Fq6B<V, D>& own, bool h, bool q) {
+  FqN r[3];
+  accdot::sqr_lane(own, h, q, DppEx{}, r);
+  const accdot::N6 P = join_q(r);
+  return accdot::sqr_fin(P, bc6<BH1>(P), h);
+}
+
+// own *= line: three dot6 per lane (accdot::line_lane); N form
 template <uint64_t V, uint64_t D, uint64_t VL, uint64_t DL, uint64_t VM, uint64_t DM>
-__device__ __forceinline__ auto qq_line(const Fq6B<V, D>& own, bool h, bool q, const Fq2B<VL, DL>& l0,
-                                        const Fq2B<VM, DM>& l2, const Fq2B<VM, DM>& l3) {
-  // the other half's coefficients are exchanged one at a time, right before their product (live range)
-  const auto p1 = sel(q, norm(own.c0 + own.c1), own.c0) * sel(q, norm(l0 + l2), l0);
-  SEQ();
-  const auto p2 = sel(q, dh2(own.c2), own.c1) * sel(q, l3, l2);
-  SEQ();
-  const auto p3 = sel(q, dh2(own.c0), own.c2) * sel(q, l3, l2);
-  SEQ();
-  const auto p4 = sel(q, dh2(own.c1), own.c2) * sel(q, l3, l0);
-  SEQ();
-  const auto t0 = bc2<BQ0>(p1), t1 = bc2<BQ0>(p2), u0 = bc2<BQ0>(p3), u2 = bc2<BQ0>(p4);  // q = 0 products
-  const auto u1 = bc2<BQ1>(p1), v0 = bc2<BQ1>(p2), v1 = bc2<BQ1>(p3), v2 = bc2<BQ1>(p4);  // q = 1 products
-  const auto m01 = fq6b(t0 + xi(u0), (u1 - (t0 + t1)), t1 + u2);
-  const auto m1 = fq6b(xi(v0), v1, v2);
-  return norm(norm(m01) + sel(h, m1, f6v(m1)));
+__device__ __forceinline__ accdot::N6 qq_line(const Fq6B<V, D>& own, bool h, bool q, const Fq2B<VL, DL>& l0,
+                                              const Fq2B<VM, DM>& l2, const Fq2B<VM, DM>& l3) {
+  FqN r[3];
+  accdot::line_lane(own, h, q, l0, l2, l3, DppEx{}, r);
+  return join_q(r);
 }
 
 // one line's inputs on lane (h, q): l0 and the coefficient this lane scales (component q of l2 for h = 0, of
@@ -297,7 +310,7 @@ __global__ void __launch_bounds__(64) k_miller_acc4q(const G1A* P, const G2A* Q,
 //   f M: a M0 (h = 0) and b M1 (h = 1) split over q, then (a + b)(M0 + M1)
 //        over all four lanes: 18 products
 // -- 12 Fp2 products per lane per round against 16 for four f x line
-// products (k_miller_acc4q<4>: 4 per line).  The exchanges are quad DPP moves
+// products (k_miller_acc4q<4> in its Karatsuba form: 4 per line).  The exchanges are quad DPP moves
 // as in k_miller_acc4q (broadcast from quad lane j: quad_perm [j, j, j, j]).
 namespace {
 
@@ -464,7 +477,7 @@ __global__ void __launch_bounds__(64) k_miller_acc4l(const G1A* P, const G2A* Q,
     }
     return;
   }
-  constexpr uint64_t VF = ML_QF_V, DF = ML_QF_D;
+  constexpr uint64_t VF = ML_QK_V, DF = ML_QK_D;
   using F = Fq6B<VF, DF>;
   const size_t step = (size_t)ML_WORDS * ld;
   const uint32_t* La = L + pi[0];
@@ -622,7 +635,7 @@ __global__ void __launch_bounds__(64) k_miller_acc8(const G1A* P, const G2A* Q, 
     }
     return;
   }
-  constexpr uint64_t VF = ML_QF_V, DF = ML_QF_D;
+  constexpr uint64_t VF = ML_QK_V, DF = ML_QK_D;
   using F = Fq6B<VF, DF>;
   const size_t step = (size_t)ML_WORDS * ld;
   const uint32_t* Lp = L + pi;
