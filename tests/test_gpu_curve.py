@@ -11,6 +11,7 @@ import os
 
 import pytest
 
+from dispatch_edge_inputs import non_subgroup_g1 as _non_subgroup_g1
 from oracle import bls_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -35,18 +36,6 @@ def setup():
 
 def _gt_bytes(f):
     return b"".join(c[0].to_bytes(48, "big") + c[1].to_bytes(48, "big") for c in O.f12_to_coeffs(f))
-
-
-def _non_subgroup_g1():
-    """A point of E1(Fp) outside G1 (the cofactor is not 1): the first x >= 1 with x^3 + 4 a square."""
-    x = 1
-    while True:
-        y = O.fp_sqrt((x ** 3 + 4) % O.P)
-        if y is not None:
-            pt = (x, y)
-            if not O.g1_in_subgroup(pt):
-                return pt
-        x += 1
 
 
 def _non_subgroup_g2():
