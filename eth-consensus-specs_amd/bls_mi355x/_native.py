@@ -77,6 +77,10 @@ _SIGS = {
     "bls_fav_batch_committee_bits": (_ip, [_vp, _vp, _vp, _vp, _vp, _sz, _u8p, _sz, _vp, _u8p, _ip, _vp]),
     "bls_fav_job_submit_bits_dev": (_ip, [_vp, _ip, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _ip, _u8p]),
     "bls_last_gather_work": (_ip, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "bls_fav_batch_keys": (_ip, [_vp, _u8p, _sz, _vp, _vp, _sz, _u8p, _sz, _vp, _u8p, _vp, _vp]),
+    "bls_verify_batch_keys": (_ip, [_vp, _u8p, _sz, _u8p, _sz, _vp, _u8p, _vp]),
+    "bls_fav_job_submit_keys_dev": (_ip, [_vp, _ip, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _u8p]),
+    "bls_deposits_verify": (_ip, [_vp, _u8p, _u8p, _vp, _u8p, _u8p, _sz, _vp, _vp]),
     "bls_aggregate_verify_batch": (_ip, [_vp, _u8p, _u8p, _vp, _vp, _sz, _u8p, _vp]),
     "bls_registry_append": (_ip, [_vp, _u8p, _sz, _vp]),
     "bls_signing_roots": (_ip, [_vp, _u8p, _u8p, _sz, _sz, _vp]),

@@ -226,6 +226,118 @@ def verify_batch_shared(indices, table, msg_ids, sigs96, ctx=None) -> np.ndarray
     return out.astype(bool)
 
 
+def key_table(pubkey_lists) -> tuple[bytes, np.ndarray, np.ndarray]:
+    """Deduplicate the keys of B key lists on the host: (table, idx, offsets) with the distinct 48-byte keys in
+    order of first occurrence, idx (uint32) the table entry of every key of every list in order, and offsets
+    (uint64, B + 1) the lists' bounds in idx -- the arguments of fast_aggregate_verify_batch_keys.  A block's
+    attestations over a small state reuse few keys, so the table (whose every entry costs the batch a KeyValidate)
+    stays short.  A key repeated inside one list stays repeated in idx: it counts twice, as the per-call path counts
+    it."""
+    seen: dict[bytes, int] = {}
+    flat, lens = [], []
+    for keys in pubkey_lists:
+        n = 0
+        for k in keys:
+            k = bytes(k)
+            if len(k) != 48:
+                raise ValueError("pubkeys must be 48 bytes each")
+            flat.append(seen.setdefault(k, len(seen)))
+            n += 1
+        lens.append(n)
+    return b"".join(seen), np.asarray(flat, dtype=np.uint32), offsets_from_lengths(lens)
+
+
+def fast_aggregate_verify_batch_keys(table, idx, offsets, msgs32, sigs96, msg_ids=None, ctx=None,
+                                     want_key_valid: bool = False):
+    """B FastAggregateVerify calls on keys given as bytes, no registry needed or touched (bls_fav_batch_keys):
+    `table` holds K compressed keys (see key_table) and item b uses entries idx[offsets[b]: offsets[b + 1]].  The
+    verdicts are fast_aggregate_verify_batch's for the same idx / offsets on a registry loaded with `table`; with
+    msg_ids, msgs32 is a message table and item b signs entry msg_ids[b] (group_messages), as in
+    fast_aggregate_verify_batch_shared.  want_key_valid: returns (verdicts, KeyValidate mask of the table).
+
+    The batch KeyValidates all K entries every time -- what the registry does once per key.  Keys that come back
+    batch after batch (the validator set) belong in a Registry; this is for keys that are not in one."""
+    t = _u8(table)
+    if t.size % 48:
+        raise ValueError("the key table must be a multiple of 48 bytes")
+    K = t.size // 48
+    ix = np.ascontiguousarray(idx, dtype=np.uint32)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if offs.ndim != 1 or offs.size < 1 or np.any(offs[1:] < offs[:-1]) or int(offs[-1]) > ix.size:
+        raise ValueError("offsets must be non-decreasing and end inside the index array")
+    B = offs.size - 1
+    s = _u8(sigs96)
+    if s.size != 96 * B:
+        raise ValueError("need one 96-byte signature per aggregate")
+    if msg_ids is not None:
+        m, M, ids = _shared_args(msgs32, msg_ids, B)
+        ids_p = _ptr(ids)
+    else:
+        m, M, ids_p = _u8(msgs32), 0, None
+        if m.size != 32 * B:
+            raise ValueError("need one 32-byte message per aggregate")
+    c = ctx or _native.context()
+    out = np.zeros(B, dtype=np.uint8)
+    valid = np.zeros(K, dtype=np.uint8) if want_key_valid else None
+    c.check(c.lib.bls_fav_batch_keys(c.h, t.tobytes(), K, _ptr(ix), _ptr(offs), B, m.tobytes(), M, ids_p, s.tobytes(),
+                                     _ptr(out), None if valid is None else _ptr(valid)))
+    return (out.astype(bool), valid) if want_key_valid else out.astype(bool)
+
+
+def verify_batch_keys(pubkeys48, msgs32, sigs96, msg_ids=None, ctx=None) -> np.ndarray:
+    """B Verify calls on raw keys (bls_verify_batch_keys): item b's key is pubkeys48[48 b: 48 b + 48].  The keys
+    batch with one key per item; msg_ids as in fast_aggregate_verify_batch_keys."""
+    k = _u8(pubkeys48)
+    if k.size % 48:
+        raise ValueError("pubkeys must be a multiple of 48 bytes")
+    B = k.size // 48
+    s = _u8(sigs96)
+    if s.size != 96 * B:
+        raise ValueError("need one 96-byte signature per key")
+    if msg_ids is not None:
+        m, M, ids = _shared_args(msgs32, msg_ids, B)
+        ids_p = _ptr(ids)
+    else:
+        m, M, ids_p = _u8(msgs32), 0, None
+        if m.size != 32 * B:
+            raise ValueError("need one 32-byte message per key")
+    c = ctx or _native.context()
+    out = np.zeros(B, dtype=np.uint8)
+    c.check(c.lib.bls_verify_batch_keys(c.h, k.tobytes(), B, m.tobytes(), M, ids_p, s.tobytes(), _ptr(out)))
+    return out.astype(bool)
+
+
+def verify_deposits(pubkeys, withdrawal_credentials, amounts, signatures, domain, want_roots: bool = False, ctx=None):
+    """N deposit signature checks (is_valid_deposit_signature; bls_deposits_verify): verdict i is
+    Verify(pubkeys[i], compute_signing_root(DepositMessage(pubkeys[i], withdrawal_credentials[i], amounts[i]),
+    domain), signatures[i]), the roots hashed on the device and the signatures checked as one keys batch.
+    want_roots: returns (verdicts, the N signing roots).  An accepted new key is not added to any registry
+    (Registry.append is the caller's: it knows which deposits are top-ups)."""
+    pk = b"".join(bytes(k) for k in pubkeys)
+    wc = b"".join(bytes(w) for w in withdrawal_credentials)
+    sg = b"".join(bytes(s) for s in signatures)
+    N = len(pubkeys)
+    if len(pk) != 48 * N or any(len(bytes(k)) != 48 for k in pubkeys):
+        raise ValueError("pubkeys must be 48 bytes each")
+    if len(withdrawal_credentials) != N or len(wc) != 32 * N:
+        raise ValueError("need one 32-byte withdrawal credential per deposit")
+    if len(signatures) != N or len(sg) != 96 * N or any(len(bytes(s)) != 96 for s in signatures):
+        raise ValueError("need one 96-byte signature per deposit")
+    if len(amounts) != N or any(not 0 <= int(a) < 1 << 64 for a in amounts):
+        raise ValueError("need one uint64 amount per deposit")
+    if len(bytes(domain)) != 32:
+        raise ValueError("the domain must be 32 bytes")
+    amt = np.asarray([int(a) for a in amounts], dtype=np.uint64)
+    c = ctx or _native.context()
+    out = np.zeros(N, dtype=np.uint8)
+    roots = ctypes.create_string_buffer(32 * N) if want_roots and N else None
+    c.check(c.lib.bls_deposits_verify(c.h, pk, wc, _ptr(amt), sg, bytes(domain), N, _ptr(out), roots))
+    if want_roots:
+        raw = roots.raw if roots is not None else b""
+        return out.astype(bool), [raw[32 * i: 32 * i + 32] for i in range(N)]
+    return out.astype(bool)
+
+
 class Committees:
     """HBM-resident committee table of one context (bls_committees_load): every committee a list of registry
     indices, fixed for an epoch.  The device keeps each committee's key sum, so that a nearly full aggregate costs
@@ -578,7 +690,7 @@ class ResidentFavBatch:
     """
 
     def __init__(self, indices, offsets, msgs32, sigs96, ctx=None, chunks: int = 1, msg_ids=None, committees=None,
-                 committee_ids=None, bits=None, mode: str = "auto"):
+                 committee_ids=None, bits=None, mode: str = "auto", keys=None):
         """chunks > 1 splits the batch into that many equal sub-batches (uniform committee size only), each
         submitted as its own FAV job: a pass over the batch is `chunks` jobs (large shards, e.g. the C4 firehose,
         stay within one job's scratch).
@@ -590,8 +702,16 @@ class ResidentFavBatch:
         committees / committee_ids / bits (indices and offsets None): the items are (committees, participation
         bits) over a Committees table, as in fast_aggregate_verify_batch_bits; only the bit bytes, messages and
         signatures are resident, and every chunk (B divisible by chunks, any item sizes) is submitted through
-        bls_fav_job_submit_bits_dev in the given mode.  The batch runs through the job API."""
+        bls_fav_job_submit_bits_dev in the given mode.  The batch runs through the job API.
+
+        keys (a table of 48-byte compressed keys, see key_table): indices name entries of that table instead of
+        the registry; the table is resident with the batch and every submit -- each chunk submits the whole table --
+        goes through bls_fav_job_submit_keys_dev, which decodes and KeyValidates it into the job's own records.
+        Works with msg_ids and with chunks (the uniform-size rule above).  The batch runs through the job API."""
         self.committees = committees
+        self.keys, self.K = None, 0
+        if keys is not None and committees is not None:
+            raise ValueError("a batch takes a key table or a committees table, not both")
         if committees is not None:
             self._init_bits(committees, committee_ids, bits, msgs32, sigs96, ctx, chunks, msg_ids, mode)
             return
@@ -614,6 +734,12 @@ class ResidentFavBatch:
             offs = offs[: self.cb + 1]  # every chunk has the same relative offsets
         else:
             self.cb, self.n = self.B, None
+        if keys is not None:
+            t = _u8(keys)
+            if t.size % 48:
+                raise ValueError("the key table must be a multiple of 48 bytes")
+            self.K = t.size // 48
+            self.keys = DeviceBuffer(self.ctx, t)
         self.idx = DeviceBuffer(self.ctx, np.ascontiguousarray(indices, dtype=np.uint32))
         self.offs = DeviceBuffer(self.ctx, offs)
         self.msgs = DeviceBuffer(self.ctx, _u8(msgs32))
@@ -653,8 +779,8 @@ class ResidentFavBatch:
         self._chunk_job = [0] * self.chunks
 
     def partial(self, seed32: bytes | None = None) -> bytes:
-        if self.chunks > 1 or self.msg_ids is not None or self.committees is not None:
-            raise ValueError("a chunked, shared-message or bits batch runs through the job API (run_pipelined)")
+        if self.chunks > 1 or self.msg_ids is not None or self.committees is not None or self.keys is not None:
+            raise ValueError("a chunked, shared-message, bits or keys batch runs through the job API (run_pipelined)")
         seed = seed32 if seed32 is not None else os.urandom(32)
         buf = ctypes.create_string_buffer(576)
         c = self.ctx
@@ -692,6 +818,12 @@ class ResidentFavBatch:
                 self.sigs.ptr + 96 * lo, self.mode, seed32))
             return
         idx, msgs, sigs, _ = self._chunk_ptrs(chunk)
+        if self.keys is not None:
+            shared = self.msg_ids is not None
+            c.check(c.lib.bls_fav_job_submit_keys_dev(c.h, job, self.keys.ptr, self.K, idx, self.offs.ptr, self.cb,
+                                                      msgs, self.M, _ptr(self.msg_ids) if shared else None, sigs,
+                                                      seed32))
+            return
         if self.msg_ids is not None:
             c.check(c.lib.bls_fav_job_submit_shared_dev(c.h, job, idx, self.offs.ptr, self.cb, msgs, self.M,
                                                         _ptr(self.msg_ids), sigs, seed32))
@@ -765,7 +897,7 @@ class ResidentFavBatch:
                               ).astype(bool)
 
     def run(self) -> np.ndarray:
-        if self.msg_ids is not None or self.committees is not None:
+        if self.msg_ids is not None or self.committees is not None or self.keys is not None:
             self.run_pipelined([os.urandom(32)])
             return self.verdicts()
         ok = self.check_partials(self.partial())
@@ -800,7 +932,7 @@ class ResidentFavBatch:
         return _grouped_result(raw[: 96 * self.M], raw[96 * self.M:])
 
     def free(self):
-        for b in (self.idx, self.offs, getattr(self, "bits", None), self.msgs, self.sigs, *self.outs):
+        for b in (self.idx, self.offs, getattr(self, "bits", None), self.keys, self.msgs, self.sigs, *self.outs):
             if b is not None:
                 b.free()
 

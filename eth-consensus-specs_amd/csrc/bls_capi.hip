@@ -8,7 +8,10 @@
 //     committee table.  bits_plan has then checked the arguments and left the host tables in the job; a pre-stage
 //     expands every item into the list its gather adds, and the gather variant of bls_gather_bits.hip writes the
 //     same apka / gstat the index gather would have written for the expanded list.  Nothing after them knows the
-//     difference.
+//     difference.  Or -- keys non-null, never together with bits -- index lists into a table of K compressed keys
+//     that belongs to the batch: a pre-stage decodes and KeyValidates it into the job's own RegKey records
+//     (S_KTAB), and the index gather runs on those records and K in place of the registry and its size.  No
+//     registry is needed or touched.
 //   messages: one per item, or -- msg_id non-null (host, B entries) -- a table of M messages of which item i signs
 //     entry msg_id[i].  The per-item stages (gather, decode, r_i apk_i chains, MSM) run over the B items as ever;
 //     the per-message stages (hash_to_G2, G2 lines, f accumulation) run over M + MSM_UPAIRS pairs whose G1 side is
@@ -17,6 +20,11 @@ struct BitsArgs {
   const uint8_t* bits;  // the items' bit bytes, item b at bit_offs[b]
   size_t bytes;         // their total (fav_batch_host's upload)
   int mode;
+};
+struct KeyTable {
+  const uint8_t* keys48;  // K compressed keys
+  size_t K;
+  uint8_t* valid;  // nullable: the KeyValidate verdict per entry, one byte each
 };
 struct FavItems {
   size_t B;
@@ -28,6 +36,7 @@ struct FavItems {
   const uint32_t* msg_id;
   const uint8_t* sigs;  // 96 bytes each
   const uint8_t* seed32;  // host: the RLC seed
+  const KeyTable* keys = nullptr;
   bool shared() const { return msg_id != nullptr; }
   size_t NH() const { return shared() ? M : B; }  // messages hashed = pairs of the H side
   // pairs 0 .. NH: (r_i apk_i, H_i); pairs NH .. NH + 64: (-w_b G1, U_b), the MSM's bit-sums (bls_msm.hip).  The 64
@@ -49,6 +58,7 @@ struct FavScratch {
   uint8_t* seed;
   SegRun* runs;
   BitsItem* bitems;
+  RegKey* ktab;
   // the Miller pairs' status and G1 side: the item arrays themselves, [0, B) items then the MSM pairs -- or, shared,
   // arrays of their own, [0, M) group sums then the MSM pairs, beside item arrays of B
   int* pstat;
@@ -174,6 +184,8 @@ static int fav_scratch(bls_ctx* ctx, const FavItems& it, FavScratch& S) {
     SCR(S_BTAB, (J.bits_tab_bytes + 7) / 8, S.tab);
     SCR(S_BLIST, J.bits_tab[3 * (B + 1) - 1], S.list);
     SCR(S_BITEM, B, S.bitems);
+  } else if (it.keys) {
+    SCR(S_KTAB, it.keys->K ? it.keys->K : 1, S.ktab);  // record 0 exists for any K (keys_stage)
   } else if (const char* gv = getenv("BLS_GATHER"); gv && !strcmp(gv, "affine") && fav_gather_aff_words(B)) {
     SCR(S_GAFF, fav_gather_aff_words(B), S.gaff);  // read per batch (gather_stage)
     SCR(S_GREDO, B, S.redo);
@@ -251,6 +263,22 @@ static int bits_stage(bls_ctx* ctx, const FavItems& it, const FavScratch& S, hip
   return 0;
 }
 
+// A batch's own key table, the pre-stage of the keys form: the K compressed keys decoded and KeyValidated into the
+// job's RegKey records, verdict in REG_VALID as the registry stores it, by the KeyValidate kernels' record output
+// (launch_key_table: one launch, no G1A / ok arrays and no pack launch in between).  On stream1 in front of the gather,
+// its only reader: the hash on stream2 has forked already and does not wait for it, and the table is the job's
+// (S_KTAB), so ten jobs in flight keep ten tables.  The gather loads record 0 for an index out of range, whatever K
+// is: with K == 0 that record is zeroed, a key that is not valid.
+static int keys_stage(bls_ctx* ctx, const FavItems& it, const FavScratch& S, hipStream_t st) {
+  const KeyTable& kt = *it.keys;
+  if (!kt.K) {
+    HIPCK(hipMemsetAsync(S.ktab, 0, sizeof(RegKey), st));
+    return 0;
+  }
+  PROF2(P_KEY_VALIDATE, st, launch_key_table(st, kt.keys48, kt.K, S.ktab, kt.valid));
+  return 0;
+}
+
 static int hash_stage(bls_ctx* ctx, const FavItems& it, const FavScratch& S, hipStream_t st2) {
   PROF2(P_FAV_HASH, st2, launch_h2c(st2, it.NH(), it.msgs, nullptr, S.hcf, S.H, S.flag));
   return h2c_fallback(ctx, st2, it.NH(), it.msgs, nullptr, S.flag, S.H);
@@ -276,7 +304,9 @@ static int decode_stage(bls_ctx* ctx, const FavItems& it, const FavScratch& S, h
 static int gather_stage(bls_ctx* ctx, const FavItems& it, const FavScratch& S, hipStream_t st) {
   Job& J = *ctx->j;
   const size_t B = it.B;
-  const uint32_t nreg = (uint32_t)ctx->reg_n;
+  // the keys form gathers from the job's table (keys_stage) with the complete formulas, as the bits form does
+  const RegKey* reg = it.keys ? S.ktab : ctx->reg;
+  const uint32_t nreg = (uint32_t)(it.keys ? it.keys->K : ctx->reg_n);
   if (it.bits) {
     // the gather variant sums the expanded lists -- and, for complement items, subtracts them from the committees'
     // cached sums.  The affine gather has no such form.
@@ -287,10 +317,10 @@ static int gather_stage(bls_ctx* ctx, const FavItems& it, const FavScratch& S, h
     J.bits_items = S.bitems;
     ctx->work_job = &J;
   } else if (S.gaff) {
-    PROF(P_FAV_GATHER, launch_fav_gather_aff(st, it.idx, it.offs, B, ctx->reg, nreg, S.apka, S.gstat, S.gaff, S.redo));
-    HIPCK(launch_fav_gather_redo(st, it.idx, it.offs, B, ctx->reg, nreg, S.apka, S.gstat, S.redo));
+    PROF(P_FAV_GATHER, launch_fav_gather_aff(st, it.idx, it.offs, B, reg, nreg, S.apka, S.gstat, S.gaff, S.redo));
+    HIPCK(launch_fav_gather_redo(st, it.idx, it.offs, B, reg, nreg, S.apka, S.gstat, S.redo));
   } else {
-    PROF(P_FAV_GATHER, launch_fav_gather(st, it.idx, it.offs, B, ctx->reg, nreg, S.apka, S.gstat));
+    PROF(P_FAV_GATHER, launch_fav_gather(st, it.idx, it.offs, B, reg, nreg, S.apka, S.gstat));
   }
   return 0;
 }
@@ -373,11 +403,13 @@ static int acc_stage(bls_ctx* ctx, const FavItems& it, const FavScratch& S, hipS
 //   stream3: signature decompression + RLC scalars -> MSM bit-sums U_b of S = sum r_i sigma_i
 // two streams (stream3 == stream2, BLS_JOB_STREAMS=2, the default): stream3's work on stream1 (decode before the
 // gather, MSM after it), off the hash -> lines chain of stream2
+// a keys batch: its key-table stage on stream1 in front of the gather (keys_stage), after the hash has been enqueued
 static int fav_prepare(bls_ctx* ctx, const FavItems& it, Fp12** out_f) {
-  if (!ctx->reg || !ctx->reg_n) {
+  if (!it.keys && (!ctx->reg || !ctx->reg_n)) {  // index lists and bits read the registry; a keys batch brings its table
     ctx->err = "no registry loaded";
     return BLS_E_NOREG;
   }
+  if (it.keys && (it.bits || it.keys->K > 0xffffffffull || (it.keys->K && !it.keys->keys48))) return BLS_E_ARG;
   Job& J = *ctx->j;
   if (it.shared()) CK(shared_plan(ctx, it));
   FavScratch S;
@@ -402,6 +434,7 @@ static int fav_prepare(bls_ctx* ctx, const FavItems& it, Fp12** out_f) {
     J.bits_up_pending = true;
   }
   CK(hash_stage(ctx, it, S, st2));
+  if (it.keys) CK(keys_stage(ctx, it, S, st));
   CK(decode_stage(ctx, it, S, sd));
   HIPCK(hipEventRecord(J.ev[EV_SIG], sd));
   if (it.bits) HIPCK(hipStreamWaitEvent(st, J.ev[EV_BITS], 0));
@@ -576,9 +609,14 @@ int bls_host_seed(uint8_t* seed32) {
 }
 
 // One host-buffer FAV batch: copies in, RLC batch check, bisection on failure.  h: the batch over the caller's host
-// buffers (seed32 unused); for a bits batch bits_plan has run, and the bit bytes go up in the index list's place
-static int fav_batch_host(bls_ctx* ctx, const FavItems& h, uint8_t* out) {
+// buffers (seed32 unused); for a bits batch bits_plan has run, and the bit bytes go up in the index list's place;
+// a keys batch's key bytes go up into a slot of their own (S_IN0 still carries its index list) and its verdict bytes,
+// when asked for, come back with the verdicts.  d_msgs / d_keys (nullable): the messages / key bytes are on the
+// device already, on stream1 (bls_deposits_verify computes the one from the other there)
+static int fav_batch_host(bls_ctx* ctx, const FavItems& h, uint8_t* out, const uint8_t* d_msgs = nullptr,
+                          const uint8_t* d_keys = nullptr) {
   const size_t B = h.B;
+  if (B > 0xffffffffull || (h.keys && h.keys->K > 0xffffffffull)) return BLS_E_ARG;
   if (h.msg_id) {  // before any device call
     if (!h.M) return BLS_E_ARG;
     for (size_t b = 0; b < B; b++)
@@ -608,10 +646,26 @@ static int fav_batch_host(bls_ctx* ctx, const FavItems& h, uint8_t* out) {
     it.idx = d_idx;
     it.offs = d_offs;
   }
-  SCR(S_IN1, 32 * nmsg, d_m);
+  KeyTable kt{nullptr, 0, nullptr};
+  if (h.keys) {
+    const size_t K = h.keys->K;
+    if (K && !h.keys->keys48 && !d_keys) return BLS_E_ARG;
+    uint8_t* d_k = const_cast<uint8_t*>(d_keys);
+    if (!d_k) {
+      SCR(S_KEYS_IN, 48 * K, d_k);
+      CK(h2d(ctx, d_k, h.keys->keys48, 48 * K));
+    }
+    kt = KeyTable{d_k, K, nullptr};
+    if (h.keys->valid) SCR(S_KVALID, K, kt.valid);
+    it.keys = &kt;
+  }
+  d_m = const_cast<uint8_t*>(d_msgs);
+  if (!d_m) {
+    SCR(S_IN1, 32 * nmsg, d_m);
+    CK(h2d(ctx, d_m, h.msgs, 32 * nmsg));
+  }
   SCR(S_IN2, 96 * B, d_s);
   SCR(S_IN3, B, d_out);
-  CK(h2d(ctx, d_m, h.msgs, 32 * nmsg));
   CK(h2d(ctx, d_s, h.sigs, 96 * B));
   uint8_t seed[32];
   CK(host_seed(ctx, seed));
@@ -627,6 +681,7 @@ static int fav_batch_host(bls_ctx* ctx, const FavItems& h, uint8_t* out) {
   if (ok < 0) return ok;
   CK(fav_finish(ctx, ok, true, d_out));
   CK(d2h(ctx, out, d_out, B));
+  if (kt.valid) CK(d2h(ctx, h.keys->valid, kt.valid, kt.K));  // each copy into caller memory is complete on return
   return 1;
 }
 
@@ -666,6 +721,74 @@ int bls_verify_batch_indexed_shared(bls_ctx* ctx, const uint32_t* idx, size_t B,
                                     const uint32_t* msg_id, const uint8_t* sigs96, uint8_t* out) {
   if (!idx && B) return BLS_E_ARG;
   return bls_fav_batch_indexed_shared(ctx, idx, identity_offsets(B).data(), B, msgs32, M, msg_id, sigs96, out);
+}
+
+// Key-table batches: the keys come as bytes with the batch, not from the registry.  B == 0 still judges the table
+// when the caller asks for the verdicts.
+int bls_fav_batch_keys(bls_ctx* ctx, const uint8_t* keys48, size_t K, const uint32_t* idx, const uint64_t* offsets,
+                       size_t B, const uint8_t* msgs32, size_t M, const uint32_t* msg_id, const uint8_t* sigs96,
+                       uint8_t* out, uint8_t* out_key_valid) {
+  API_ENTER(ctx);
+  if (K > 0xffffffffull || B > 0xffffffffull || (!keys48 && K)) return BLS_E_ARG;
+  if ((!offsets || !msgs32 || !sigs96 || !out) && B) return BLS_E_ARG;
+  if (!B) {
+    if (out_key_valid && K) {
+      uint8_t *d_k, *d_v;
+      RegKey* tab;
+      SCR(S_KEYS_IN, 48 * K, d_k);
+      SCR(S_KVALID, K, d_v);
+      SCR(S_KTAB, K, tab);
+      CK(h2d(ctx, d_k, keys48, 48 * K));
+      HIPCK(launch_key_table(ctx->j->stream, d_k, K, tab, d_v));
+      CK(d2h(ctx, out_key_valid, d_v, K));
+    }
+    return 1;
+  }
+  const KeyTable kt{keys48, K, out_key_valid};
+  return fav_batch_host(ctx, FavItems{B, idx, offsets, nullptr, msgs32, msg_id ? M : 0, msg_id, sigs96, nullptr, &kt},
+                        out);
+}
+
+static std::vector<uint32_t> identity_indices(size_t B) {  // item b's key is table entry b
+  std::vector<uint32_t> idx(B);
+  for (size_t i = 0; i < B; i++) idx[i] = (uint32_t)i;
+  return idx;
+}
+
+int bls_verify_batch_keys(bls_ctx* ctx, const uint8_t* keys48, size_t B, const uint8_t* msgs32, size_t M,
+                          const uint32_t* msg_id, const uint8_t* sigs96, uint8_t* out) {
+  if (B > 0xffffffffull) return BLS_E_ARG;
+  return bls_fav_batch_keys(ctx, keys48, B, identity_indices(B).data(), identity_offsets(B).data(), B, msgs32, M,
+                            msg_id, sigs96, out, nullptr);
+}
+
+// N deposit signatures: the signing roots on the device (k_deposit_roots) from the uploaded keys, credentials and
+// amounts, then the keys batch of one key per item on the same job -- table = the N keys, idx = the identity,
+// messages = the roots where the kernel left them.
+int bls_deposits_verify(bls_ctx* ctx, const uint8_t* pubkeys48, const uint8_t* wc32, const uint64_t* amounts,
+                        const uint8_t* sigs96, const uint8_t* domain32, size_t N, uint8_t* out, uint8_t* out_roots32) {
+  API_ENTER(ctx);
+  if (N > 0xffffffffull || ((!pubkeys48 || !wc32 || !amounts || !sigs96 || !domain32 || !out) && N)) return BLS_E_ARG;
+  if (!N) return 1;
+  uint8_t *d_k, *d_wc, *d_dom, *d_roots;
+  uint64_t* d_amt;
+  SCR(S_KEYS_IN, 48 * N, d_k);
+  SCR(S_SZ_A, 32 * N, d_wc);
+  SCR(S_SZ_B, N, d_amt);
+  SCR(S_SZ_Z, 32, d_dom);
+  SCR(S_IN1, 32 * N, d_roots);
+  CK(h2d(ctx, d_k, pubkeys48, 48 * N));
+  CK(h2d(ctx, d_wc, wc32, 32 * N));
+  CK(h2d(ctx, d_amt, amounts, 8 * N));
+  CK(h2d(ctx, d_dom, domain32, 32));
+  HIPCK(launch_deposit_roots(ctx->j->stream, d_k, d_wc, d_amt, d_dom, N, d_roots));
+  // synchronous: no copy into the caller's buffer is pending if the batch below returns an error
+  if (out_roots32) CK(d2h(ctx, out_roots32, d_roots, 32 * N));
+  const KeyTable kt{pubkeys48, N, nullptr};
+  const std::vector<uint32_t> idx = identity_indices(N);
+  const std::vector<uint64_t> offs = identity_offsets(N);
+  return fav_batch_host(ctx, FavItems{N, idx.data(), offs.data(), nullptr, nullptr, 0, nullptr, sigs96, nullptr, &kt},
+                        out, d_roots, d_k);
 }
 
 int bls_fav_batch_committee_bits(bls_ctx* ctx, const uint32_t* comm_ids, const uint64_t* comm_offs,
@@ -905,6 +1028,19 @@ int bls_fav_job_submit_bits_dev(bls_ctx* ctx, int job, const uint32_t* comm_ids,
   const BitsArgs ba{d_bits, 0, mode};
   return job_submit_exchange(ctx, r, FavItems{B, nullptr, nullptr, B ? &ba : nullptr, d_msgs32, msg_id ? M : 0,
                                               B ? msg_id : nullptr, d_sigs96, seed32});
+}
+
+// The key-table form: d_keys48 (K keys) device resident like the index lists; msg_id == nullptr: one message per
+// item.  An empty shard (B == 0, the device exchange only) takes no table.
+int bls_fav_job_submit_keys_dev(bls_ctx* ctx, int job, const uint8_t* d_keys48, size_t K, const uint32_t* d_idx,
+                                const uint64_t* d_offsets, size_t B, const uint8_t* d_msgs32, size_t M,
+                                const uint32_t* msg_id, const uint8_t* d_sigs96, const uint8_t* seed32) {
+  JOB_ENTER(ctx, job);
+  const int r = (K > 0xffffffffull || B > 0xffffffffull || (K && !d_keys48)) ? BLS_E_ARG : 0;
+  const KeyTable kt{d_keys48, K, nullptr};
+  FavItems it{B, d_idx, d_offsets, nullptr, d_msgs32, msg_id ? M : 0, B ? msg_id : nullptr, d_sigs96, seed32};
+  if (B) it.keys = &kt;
+  return job_submit_exchange(ctx, r, it);
 }
 
 int bls_fav_job_partial(bls_ctx* ctx, int job, uint8_t* partial576) {

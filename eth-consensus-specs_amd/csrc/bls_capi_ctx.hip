@@ -84,6 +84,13 @@ hipError_t launch_keys(hipStream_t st, const uint8_t* pks, size_t n, G1A* out, i
   return n <= WIDE_KEYS_MAX ? launch_key_validate_wide(st, pks, n, out, ok) : launch_key_validate(st, pks, n, out, ok);
 }
 
+// a keys batch's table (bls_fav_batch_keys): the same two kernels and the same switch, writing RegKey records with
+// the verdict in REG_VALID straight from the key bytes (bls_key_out.h); valid (nullable): the verdicts as bytes
+hipError_t launch_key_table(hipStream_t st, const uint8_t* pks, size_t n, RegKey* rec, uint8_t* valid) {
+  return n <= WIDE_KEYS_MAX ? launch_key_records_wide(st, pks, n, rec, valid)
+                            : launch_key_records(st, pks, n, rec, valid);
+}
+
 // the pairing APIs' decodes of n (G1, G2) pairs at d_in (48 n bytes of G1, then 96 n of G2), identity accepted: with
 // the subgroup checks on the wide kernels (latency; up to WIDE_KEYS_MAX pairs), unchecked or beyond on the lane kernels
 hipError_t launch_pairs_decode(hipStream_t st, const uint8_t* d_in, size_t n, bool subgroup, G1A* P, G2A* Q,

@@ -55,6 +55,10 @@ enum Slot {
   // -- committees | bit bytes | list slots, B + 1 each -- then the items' committee ids), the expanded index lists
   // and the item records
   S_BTAB, S_BLIST, S_BITEM,
+  // key-table batches (FavItems::keys): the job's own table of RegKey records, decoded and KeyValidated from the
+  // batch's key bytes (at least one record: the gather's unconditional load of record 0), and for the host-buffer
+  // entry points the uploaded key bytes and the verdict bytes that go back
+  S_KTAB, S_KEYS_IN, S_KVALID,
   NSLOT
 };
 
@@ -214,6 +218,7 @@ int run_final_checks_sel(bls_ctx* ctx, const Fp12* f, const uint32_t* sel, size_
 int h2c_fallback(bls_ctx* ctx, hipStream_t st, size_t B, const uint8_t* msgs, const uint64_t* offs, int* flag, G2A* H);
 int validate_pks(bls_ctx* ctx, const uint8_t* pks, size_t n, G1A** outA, int** outOk);
 hipError_t launch_keys(hipStream_t st, const uint8_t* pks, size_t n, G1A* out, int* ok);
+hipError_t launch_key_table(hipStream_t st, const uint8_t* pks, size_t n, RegKey* rec, uint8_t* valid);
 hipError_t launch_pairs_decode(hipStream_t st, const uint8_t* d_in, size_t n, bool subgroup, G1A* P, G2A* Q, int* ok1,
                                int* ok2);
 hipError_t launch_miller_call(hipStream_t st, const G1A* P, const G2A* Q, size_t n, Fp12* f, size_t* nf,

@@ -5,6 +5,12 @@
 namespace bls {
 
 hipError_t launch_key_validate(hipStream_t st, const uint8_t* pks, size_t n, G1A* out, int* ok);
+// the same kernel writing RegKey records (verdict in REG_VALID, a failed key zeroed) straight from the key bytes:
+// the key table of a keys batch; valid (nullable): the verdicts as bytes (bls_key_out.h)
+hipError_t launch_key_records(hipStream_t st, const uint8_t* pks, size_t n, RegKey* rec, uint8_t* valid);
+// SSZ signing roots of n deposits (bls_ssz.hip): five 64-byte SHA-256 nodes per lane
+hipError_t launch_deposit_roots(hipStream_t st, const uint8_t* pks48, const uint8_t* wc32, const uint64_t* amounts,
+                                const uint8_t* domain32, size_t n, uint8_t* out32);
 hipError_t launch_sig_validate(hipStream_t st, const uint8_t* sigs, size_t n, G2A* out, int* ok);
 hipError_t launch_g1_sum_aff(hipStream_t st, const G1A* in, const int* ok, size_t n, G1J* tmp, G1J* out);
 hipError_t launch_g2_sum_aff(hipStream_t st, const G2A* in, const int* ok, size_t n, G2J* tmp, G2J* out);
@@ -192,6 +198,8 @@ hipError_t launch_miller_wide_n(hipStream_t st, const G1A* P, const G2A* Q, cons
 hipError_t launch_fe_wide(hipStream_t st, const Fp12* f, int n, int* out, uint64_t* ts = nullptr);  // ts: stage clocks (tests)
 // KeyValidate with two keys per wave (k_key_validate semantics)
 hipError_t launch_key_validate_wide(hipStream_t st, const uint8_t* pks, size_t n, G1A* out, int* ok);
+// ... writing RegKey records (launch_key_records on the wide kernel)
+hipError_t launch_key_records_wide(hipStream_t st, const uint8_t* pks, size_t n, RegKey* rec, uint8_t* valid);
 // the checked G1 decode (identity accepted, k_pt_decode semantics) on the wide KeyValidate kernel
 hipError_t launch_g1_decode_checked_wide(hipStream_t st, const uint8_t* in48, size_t n, G1A* out, int* ok);
 

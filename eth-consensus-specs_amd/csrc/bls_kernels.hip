@@ -6,6 +6,7 @@
 
 #include "bls_kernels.h"
 #include "bls_fq_g1.h"
+#include "bls_key_out.h"
 
 namespace bls {
 
@@ -35,7 +36,9 @@ static __device__ __forceinline__ G1Q g1q_mul_xabs(const G1Q& b) {
 //   decode: flags, x < p, y = (x^3 + 4)^((p+1)/4) (fq_pow_w3), y^2 == x^3 + 4, the sign bit picks y or -y;
 //   subgroup (bls_curve.h g1_in_subgroup): phi(P) == -[x^2] P with phi(x, y) = (beta x, y), i.e. for
 //   [|x|]([|x|] P) = (X : Y : Z):  beta x Z == X  and  y Z + Y == 0  (Z == 0, the identity, fails the second).
-__global__ void __launch_bounds__(64) k_key_validate(const uint8_t* pks48, size_t n, G1A* out, int* ok) {
+// OUT: where the result goes (bls_key_out.h) -- the point and verdict arrays, or a key table's RegKey records.
+template <class OUT>
+__global__ void __launch_bounds__(64) k_key_validate(const uint8_t* pks48, size_t n, OUT o) {
   const size_t i = gtid();
   if (i >= n) return;
   // 48 big-endian bytes; records are 48 B apart, so word loads stay 4-byte aligned
@@ -70,8 +73,7 @@ __global__ void __launch_bounds__(64) k_key_validate(const uint8_t* pks48, size_
       }
     }
   }
-  out[i] = a;
-  ok[i] = v;
+  o.put(i, a, v);
 }
 
 // ------------------------------------------------------------ reductions --
@@ -520,7 +522,12 @@ static inline unsigned nblk(size_t n, unsigned t) { return (unsigned)((n + t - 1
 
 hipError_t launch_key_validate(hipStream_t st, const uint8_t* pks, size_t n, G1A* out, int* ok) {
   if (!n) return hipSuccess;
-  LAUNCH(k_key_validate, nblk(n, 64), 64, st, pks, n, out, ok);
+  LAUNCH(k_key_validate<KeyOutPoints>, nblk(n, 64), 64, st, pks, n, KeyOutPoints{out, ok});
+  return hipSuccess;
+}
+hipError_t launch_key_records(hipStream_t st, const uint8_t* pks, size_t n, RegKey* rec, uint8_t* valid) {
+  if (!n) return hipSuccess;
+  LAUNCH(k_key_validate<KeyOutRecords>, nblk(n, 64), 64, st, pks, n, KeyOutRecords{rec, valid});
   return hipSuccess;
 }
 

@@ -2,6 +2,7 @@
 // (per-call path), and the device self-test of the wide products against the
 // lane form of bls_fq.h.
 #include "bls_kernels.h"
+#include "bls_key_out.h"
 #include "bls_lane.h"
 #include "bls_wide.h"
 #include "bls_wide_g2.h"
@@ -481,8 +482,9 @@ __device__ __forceinline__ G1W g1w_mul_xabs4(const WKG& K, const G1W& b, uint32_
 // the chains' doublings, whose products are spread over the four (g1w_dbl4).  Wave-uniform control flow: the two
 // halves' decode verdicts are combined into selects, not branches.  INF_OK: the checked G1 decode of the pairing APIs
 // (k_pt_decode semantics: the identity encoding is a valid point) instead of KeyValidate's rejection of it.
-template <bool INF_OK>
-__global__ void __launch_bounds__(256) k_key_validate_wide(const uint8_t* pks48, size_t n, G1A* out, int* ok) {
+// OUT: where the result goes (bls_key_out.h), as in k_key_validate.
+template <bool INF_OK, class OUT>
+__global__ void __launch_bounds__(256) k_key_validate_wide(const uint8_t* pks48, size_t n, OUT o) {
   const size_t base = 2 * (size_t)blockIdx.x;
   if (base >= n) return;  // (the whole workgroup)
   __shared__ uint32_t x4[8 * 64];
@@ -517,21 +519,27 @@ __global__ void __launch_bounds__(256) k_key_validate_wide(const uint8_t* pks48,
   const bool v = fmt && on && eq_x && eq_y;
   const bool id = INF_OK && c_flag && b_flag && !a_flag && fp_is_zero(x);
   const G1A a = v ? G1A{w_to_fp(xm), w_to_fp(y), false} : G1A{fp_zero(), fp_zero(), true};
-  if (wpos() == 0 && base + (size_t)h < n) {
-    out[base + h] = a;
-    ok[base + h] = v || id ? 1 : 0;
-  }
+  if (wpos() == 0 && base + (size_t)h < n) o.put(base + h, a, v || id ? 1 : 0);
 }
 
 hipError_t launch_key_validate_wide(hipStream_t st, const uint8_t* pks, size_t n, G1A* out, int* ok) {
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(k_key_validate_wide<false>, dim3((unsigned)((n + 1) / 2)), dim3(256), 0, st, pks, n, out, ok);
+  hipLaunchKernelGGL((k_key_validate_wide<false, KeyOutPoints>), dim3((unsigned)((n + 1) / 2)), dim3(256), 0, st, pks,
+                     n, KeyOutPoints{out, ok});
+  return hipGetLastError();
+}
+
+hipError_t launch_key_records_wide(hipStream_t st, const uint8_t* pks, size_t n, RegKey* rec, uint8_t* valid) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL((k_key_validate_wide<false, KeyOutRecords>), dim3((unsigned)((n + 1) / 2)), dim3(256), 0, st, pks,
+                     n, KeyOutRecords{rec, valid});
   return hipGetLastError();
 }
 
 hipError_t launch_g1_decode_checked_wide(hipStream_t st, const uint8_t* in48, size_t n, G1A* out, int* ok) {
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(k_key_validate_wide<true>, dim3((unsigned)((n + 1) / 2)), dim3(256), 0, st, in48, n, out, ok);
+  hipLaunchKernelGGL((k_key_validate_wide<true, KeyOutPoints>), dim3((unsigned)((n + 1) / 2)), dim3(256), 0, st, in48,
+                     n, KeyOutPoints{out, ok});
   return hipGetLastError();
 }
 

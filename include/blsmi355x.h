@@ -208,6 +208,38 @@ int bls_fav_batch_committee_bits(bls_ctx* ctx, const uint32_t* comm_ids, const u
  * the number of complement items.  Waits for that batch's gather.  Returns 0. */
 int bls_last_gather_work(bls_ctx* ctx, uint64_t* points_added, uint64_t* complement_items);
 
+/* Key-table batches: B FastAggregateVerify calls on keys given as bytes.
+ * keys48: a table of K compressed keys (duplicates allowed); item b uses table
+ * entries idx[offsets[b] .. offsets[b+1]).  Messages: one per item (msg_id
+ * NULL, M ignored) or a table of M with msg_id[b] < M, as in
+ * bls_fav_batch_indexed_shared.  out[b] is what bls_fav_batch_indexed(_shared)
+ * returns for the same idx / offsets on a registry loaded with keys48 -- i.e.
+ * bls_fast_aggregate_verify on the item's keys:
+ *   - a member that fails KeyValidate -> 0;
+ *   - an index >= K -> 0;
+ *   - an empty item -> 0;
+ *   - the same key twice in an item counts twice.
+ * out_key_valid (nullable, K bytes): the KeyValidate verdict per table entry
+ * (with B == 0 the table is still judged when this is given).
+ * The batch decodes and KeyValidates the table itself, into records of its
+ * own, and then runs the indexed batch's pipeline on them: the RLC check, the
+ * MSM and split Miller loop, the bisection on failure.  It needs no registry
+ * and touches none: size, generation, committee table and any batch in flight
+ * on another job are unaffected.  The price is K KeyValidates per batch, which
+ * the registry pays once per key: keys that are used across batches -- the
+ * validator set -- belong in the registry (bls_registry_load / _append); this
+ * form is for keys that are not there (deposits, withdrawal keys, a run that
+ * has loaded no registry).
+ * K == 0 is allowed (every verdict 0).  K or B > 2^32 - 1, a bad msg_id,
+ * M == 0 with msg_id: BLS_E_ARG before any device call.  Returns 1 or BLS_E_*. */
+int bls_fav_batch_keys(bls_ctx* ctx, const uint8_t* keys48, size_t K, const uint32_t* idx, const uint64_t* offsets,
+                       size_t B, const uint8_t* msgs32, size_t M, const uint32_t* msg_id, const uint8_t* sigs96,
+                       uint8_t* out, uint8_t* out_key_valid);
+/* One key per item: item b's key is table entry b (K == B) -- B Verify calls
+ * on raw keys. */
+int bls_verify_batch_keys(bls_ctx* ctx, const uint8_t* keys48, size_t B, const uint8_t* msgs32, size_t M,
+                          const uint32_t* msg_id, const uint8_t* sigs96, uint8_t* out);
+
 /* B AggregateVerify calls <- E/utils/bls.py:154-164 (one call per item).
  * Item b owns the pairs item_offs[b] .. item_offs[b+1] (item_offs has B+1
  * entries, total = item_offs[B]): pubkeys pks48[48 t ..], messages
@@ -238,6 +270,17 @@ int bls_signing_roots(bls_ctx* ctx, const uint8_t* object_roots32, const uint8_t
  * (depth >= ceil(log2 n); missing leaves are zero chunks).  n = 0 gives the
  * zero-subtree root of that depth.  Returns 1 or BLS_E_*. */
 int bls_merkleize(bls_ctx* ctx, const uint8_t* chunks32, size_t n, int depth, uint8_t* root32);
+/* N deposit signature checks (is_valid_deposit_signature,
+ * specs/electra/beacon-chain.md:1577-1588): message i is
+ * compute_signing_root(DepositMessage(pubkey_i, wc_i, amount_i), domain32),
+ * computed on the device (five SHA-256 nodes per deposit).
+ * out[i] = bls_verify(pubkey_i, that root, sig_i), through
+ * bls_verify_batch_keys's path (table = the N keys).  out_roots32 (nullable):
+ * the N signing roots.  Appending the accepted new keys to the registry is
+ * the caller's (bls_registry_append: which deposits are top-ups is its
+ * knowledge).  Returns 1 or BLS_E_*. */
+int bls_deposits_verify(bls_ctx* ctx, const uint8_t* pubkeys48, const uint8_t* wc32, const uint64_t* amounts,
+                        const uint8_t* sigs96, const uint8_t* domain32, size_t N, uint8_t* out, uint8_t* out_roots32);
 
 /* ---- KZG pieces ---------------------------------- */
 /* pairing_check  <- E/utils/bls.py pairing_check (used by
@@ -358,6 +401,17 @@ int bls_fav_job_submit_bits_dev(bls_ctx* ctx, int job, const uint32_t* comm_ids,
                                 const uint8_t* d_bits, const uint64_t* bit_offs, size_t B, const uint8_t* d_msgs32,
                                 size_t M, const uint32_t* msg_id, const uint8_t* d_sigs96, int mode,
                                 const uint8_t* seed32);
+/* The key-table form of submit (bls_fav_batch_keys): d_keys48 (K keys),
+ * d_idx, d_offsets, d_msgs32 (B messages, or with msg_id a table of M) and
+ * d_sigs96 are device resident, msg_id is a HOST array (nullable) as in the
+ * shared form.  d_keys48 must be 4-byte aligned (the kernels read the key
+ * bytes as 32-bit words; any bls_dev_alloc / hipMalloc base is, and so is any
+ * offset of whole keys from one).  The decoded table is the job's own, so
+ * jobs in flight together each keep theirs.  partial / check / check_own / check_comm /
+ * finish are the calls below, unchanged. */
+int bls_fav_job_submit_keys_dev(bls_ctx* ctx, int job, const uint8_t* d_keys48, size_t K, const uint32_t* d_idx,
+                                const uint64_t* d_offsets, size_t B, const uint8_t* d_msgs32, size_t M,
+                                const uint32_t* msg_id, const uint8_t* d_sigs96, const uint8_t* seed32);
 int bls_fav_job_partial(bls_ctx* ctx, int job, uint8_t* partial576);
 int bls_fav_job_check(bls_ctx* ctx, int job, const uint8_t* partials576, size_t n);
 /* check_own: the final exponentiation of the job's own product alone, which
