@@ -114,6 +114,12 @@ _SIGS = {
     "bls_point_mul": (_ip, [_vp, _ip, _u8p, _u8p, _vp]),
     "bls_point_neg": (_ip, [_vp, _ip, _u8p, _vp]),
     "bls_multi_exp": (_ip, [_vp, _ip, _u8p, _u8p, _sz, _ip, _vp]),
+    "bls_g1_table_load": (_ip, [_vp, _u8p, _sz, _ip, _vp]),
+    "bls_g1_table_append": (_ip, [_vp, _u8p, _sz, _ip, _vp]),
+    "bls_g1_table_size": (_sz, [_vp]),
+    "bls_g1_table_generation": (ctypes.c_uint64, [_vp]),
+    "bls_g1_table_msm": (_ip, [_vp, _vp, _sz, _vp, _sz, _vp]),
+    "bls_g1_table_stats": (_ip, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "bls_multi_pairing": (_ip, [_vp, _u8p, _u8p, _sz, _ip, _vp]),
     "bls_gt_mul": (_ip, [_vp, _u8p, _u8p, _vp]),
     "bls_pairing_check_ex": (_ip, [_vp, _u8p, _u8p, _sz, _ip]),

@@ -608,7 +608,10 @@ def pairing_check(pairs, ctx=None) -> bool:
 def g1_multi_exp(points48, scalars, ctx=None, subgroup_check: bool = False) -> bytes:
     """KZG multi_exp / g1_lincomb on compressed points: sum [k_i] P_i (E/utils/bls.py:262-296 -> arkworks
     G1.multiexp_unchecked, i.e. no subgroup check unless asked); scalars are ints (0 <= k < 2^256).  Raises on
-    an empty input (E/utils/bls.py:270-271) and on an invalid encoding, like the reference."""
+    an empty input (E/utils/bls.py:270-271) and on an invalid encoding, like the reference.
+
+    Every call copies and decompresses every point again.  For a point set that is multiplied repeatedly (the KZG
+    trusted setup), load it once into a ``G1Table`` and use ``g1_lincomb_indexed`` / ``g1_lincomb_batch``."""
     c = ctx or _native.context()
     pts = [bytes(p) for p in points48]
     ks = [int(k) for k in scalars]
@@ -627,6 +630,145 @@ def g1_multi_exp(points48, scalars, ctx=None, subgroup_check: bool = False) -> b
     if rc != 1:
         raise ValueError("invalid G1 point encoding")
     return out.raw
+
+
+class G1Table:
+    """HBM-resident G1 point table of one context (``bls_g1_table_*``): the points are decoded once and kept with
+    their window multiples, so that ``g1_lincomb_indexed`` / ``g1_lincomb_batch`` over them add only.
+
+    The host keeps a point-bytes -> index map for what was loaded or appended through this object, tied to the
+    library's table generation as ``Registry``'s map is: after another object replaces the device table, lookups
+    return None.  ``checked`` says whether every entry went through the subgroup check; ``usable(i)`` whether
+    entry i decoded (an invalid encoding keeps its index and makes an MSM that names it raise)."""
+
+    def __init__(self, ctx: _native.Context | None = None):
+        self.ctx = ctx or _native.context()
+        self._index: dict[bytes, int] = {}
+        self._ok = np.zeros(0, dtype=np.uint8)
+        self._gen = None
+        self.checked = False
+
+    def _generation(self) -> int:
+        return int(self.ctx.lib.bls_g1_table_generation(self.ctx.h))
+
+    def _current(self) -> bool:
+        return self._gen is not None and self._gen == self._generation()
+
+    @staticmethod
+    def _points(points48) -> np.ndarray:
+        if isinstance(points48, (bytes, bytearray, memoryview, np.ndarray)):
+            buf = _u8(points48)
+        else:
+            buf = _u8(b"".join(bytes(p) for p in points48))
+        if buf.size % 48:
+            raise ValueError("points must be 48 bytes each")
+        return buf
+
+    def _remember(self, buf: np.ndarray, first: int, ok: np.ndarray) -> None:
+        raw = buf.tobytes()
+        for i in range(len(raw) // 48):
+            self._index.setdefault(raw[48 * i: 48 * i + 48], first + i)
+        self._ok = np.concatenate([self._ok[:first], ok])
+
+    def load(self, points48, subgroup_check: bool = False) -> np.ndarray:
+        """Replace the table with these compressed points (one bytes object or a sequence of 48-byte encodings);
+        returns the per-encoding verdicts (1 = decodes and, with subgroup_check, lies in G1)."""
+        buf = self._points(points48)
+        n = buf.size // 48
+        ok = np.zeros(n, dtype=np.uint8)
+        c = self.ctx
+        self._index, self._gen, self._ok = {}, None, np.zeros(0, dtype=np.uint8)
+        c.check(c.lib.bls_g1_table_load(c.h, buf.tobytes(), n, 1 if subgroup_check else 0, _ptr(ok)))
+        self.checked = bool(subgroup_check)
+        self._remember(buf, 0, ok)
+        self._gen = self._generation()
+        return ok
+
+    def append(self, points48, subgroup_check: bool = False) -> np.ndarray:
+        """Add points at indices len(self) ..; existing indices stay."""
+        buf = self._points(points48)
+        n = buf.size // 48
+        first = len(self)
+        ok = np.zeros(n, dtype=np.uint8)
+        c = self.ctx
+        c.check(c.lib.bls_g1_table_append(c.h, buf.tobytes(), n, 1 if subgroup_check else 0, _ptr(ok)))
+        if self._current():
+            self.checked = self.checked and bool(subgroup_check)
+            self._remember(buf, first, ok)
+        return ok
+
+    def indices(self, points) -> np.ndarray | None:
+        """u32 table indices of every point (bytes-like encodings), or None if any is absent or the map is stale."""
+        if not self._current():
+            return None
+        out = np.empty(len(points), dtype=np.uint32)
+        for i, p in enumerate(points):
+            k = self._index.get(bytes(p))
+            if k is None:
+                return None
+            out[i] = k
+        return out
+
+    def usable(self, i: int) -> bool:
+        return self._current() and 0 <= i < self._ok.size and bool(self._ok[i])
+
+    def all_usable(self, idx: np.ndarray) -> bool:
+        """whether every index of an ``indices()`` result names an entry that decoded"""
+        return self._current() and bool(self._ok[idx].all())
+
+    def __len__(self):
+        return int(self.ctx.lib.bls_g1_table_size(self.ctx.h))
+
+
+def _lincomb_rows(scalar_rows, n: int) -> bytes:
+    rows = []
+    for row in scalar_rows:
+        ks = [int(k) for k in row]
+        if len(ks) != n:
+            raise ValueError("one scalar per index in every row")
+        if any(not 0 <= k < 1 << 256 for k in ks):
+            raise ValueError("need 256-bit scalars")
+        rows.append(b"".join(k.to_bytes(32, "big") for k in ks))
+    return b"".join(rows)
+
+
+def g1_lincomb_batch(table: G1Table, idx, scalar_rows) -> list:
+    """B linear combinations over one shared index list in one call (``bls_g1_table_msm``): result[v] =
+    sum_i [scalar_rows[v][i]] T[idx[i]], 48 compressed bytes each.  Scalars are ints 0 <= k < 2^256 and are taken
+    as integer multiples, as the C ABI takes them (no reduction mod r here: reduce first, as ``g1_multi_exp``
+    does, where the table holds points outside G1).  Raises ValueError on an empty index list (the reference
+    raises on an empty multi_exp), on an index outside the table and when an index names an entry whose encoding
+    was invalid at load."""
+    a_idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    if a_idx.ndim != 1 or a_idx.size == 0:
+        raise ValueError("Cannot call multi_exp with zero points or zero scalars")
+    n = a_idx.size
+    rows = _lincomb_rows(scalar_rows, n)
+    B = len(rows) // (32 * n)
+    if B == 0:
+        return []
+    c = table.ctx
+    out = ctypes.create_string_buffer(48 * B)
+    rc = c.lib.bls_g1_table_msm(c.h, _ptr(a_idx), n, rows, B, out)
+    if rc == _native.BLS_E_ARG:
+        raise ValueError("index outside the G1 table, or too many scalars for one call")
+    if c.check(rc) != 1:
+        raise ValueError("an index names an invalid G1 point encoding")
+    return [out.raw[48 * v: 48 * v + 48] for v in range(B)]
+
+
+def g1_lincomb_indexed(table: G1Table, idx, scalars) -> bytes:
+    """sum_i [scalars[i]] T[idx[i]] over a resident table: ``g1_lincomb_batch`` with one row."""
+    return g1_lincomb_batch(table, idx, [scalars])[0]
+
+
+def g1_table_stats(ctx=None) -> tuple[int, int, int]:
+    """(table MSM calls, bucket entries added, decode hits served from the table) since the context was created:
+    the first two from the library, the third counted by ``curve.G1Point`` while ``curve.use_g1_table`` is set."""
+    c = ctx or _native.context()
+    calls, entries = ctypes.c_uint64(), ctypes.c_uint64()
+    c.check(c.lib.bls_g1_table_stats(c.h, ctypes.byref(calls), ctypes.byref(entries)))
+    return int(calls.value), int(entries.value), int(getattr(c, "g1_decode_hits", 0))
 
 
 def fallback_stats(ctx=None) -> tuple[int, int]:

@@ -39,6 +39,29 @@ def _ctx():
     return _native.context()
 
 
+_g1_table = None  # the batch.G1Table that G1Point decodes and multi-exponentiations consult (use_g1_table)
+
+
+def use_g1_table(table) -> None:
+    """Route ``G1Point`` through a resident point table (``batch.G1Table``), or back with None.  While a table is
+    set, ``G1Point.multiexp*`` over points that are all usable entries of it runs ``bls_g1_table_msm`` on their
+    indices, and decoding bytes that are a usable entry returns without a device call.  A request for the subgroup
+    check is served from the table only if every entry was loaded with it; anything else takes the route it takes
+    with no table set, unchanged."""
+    global _g1_table
+    _g1_table = table
+
+
+def _table_indices(table, encodings, subgroup: int):
+    """indices of the encodings in the table when the table may serve this request, else None"""
+    if table is None or (subgroup and not table.checked):
+        return None
+    idx = table.indices(encodings)
+    if idx is None or not table.all_usable(idx):
+        return None
+    return idx
+
+
 class Scalar:
     """Element of F_r (r = BLS_MODULUS); ints are reduced mod r on construction."""
 
@@ -165,6 +188,10 @@ class _Point:
         b = bytes(data)
         if len(b) != cls.WIDTH:
             raise ValueError(f"expected {cls.WIDTH} bytes, got {len(b)}")
+        if cls.GROUP == 1 and _g1_table is not None and _table_indices(_g1_table, [b], subgroup) is not None:
+            hit = _g1_table.ctx
+            hit.g1_decode_hits = getattr(hit, "g1_decode_hits", 0) + 1
+            return cls._wrap(b)
         c = _ctx()
         if c.check(c.lib.bls_point_decode(c.h, cls.GROUP, b, 1, subgroup, None)) != 1:
             raise ValueError("invalid compressed point encoding" + (" or not in the subgroup" if subgroup else ""))
@@ -250,6 +277,11 @@ class _Point:
             raise ValueError("one scalar per point")
         if any(type(p) is not cls for p in pts):
             raise TypeError(f"multiexp over {cls.__name__} needs {cls.__name__} points")
+        if cls.GROUP == 1 and _g1_table is not None:
+            idx = _table_indices(_g1_table, [p._b for p in pts], subgroup)
+            if idx is not None:
+                from . import batch
+                return cls._wrap(batch.g1_lincomb_indexed(_g1_table, idx, [int.from_bytes(_k32(k), "big") for k in ks]))
         c = _ctx()
         out = ctypes.create_string_buffer(cls.WIDTH)
         rc = c.check(c.lib.bls_multi_exp(c.h, cls.GROUP, b"".join(p._b for p in pts), b"".join(_k32(k) for k in ks),

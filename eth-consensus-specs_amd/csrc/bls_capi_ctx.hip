@@ -294,6 +294,8 @@ void bls_ctx_destroy(bls_ctx* ctx) {
   if (ctx->reg) (void)hipFree(ctx->reg);
   for (void* p : {(void*)ctx->ctab_idx, (void*)ctx->ctab_offs, (void*)ctx->ctab_sum, (void*)ctx->ctab_stat})
     if (p) (void)hipFree(p);
+  if (ctx->g1t) (void)hipFree(ctx->g1t);
+  if (ctx->g1t_stat) (void)hipFree(ctx->g1t_stat);
   if (ctx->comb) (void)hipFree(ctx->comb);
   if (ctx->force_fb) (void)hipFree(ctx->force_fb);
   if (ctx->pc_stage) (void)hipHostFree(ctx->pc_stage);

@@ -59,6 +59,12 @@ enum Slot {
   // batch's key bytes (at least one record: the gather's unconditional load of record 0), and for the host-buffer
   // entry points the uploaded key bytes and the verdict bytes that go back
   S_KTAB, S_KEYS_IN, S_KVALID,
+  // resident G1 table (bls_capi_msm.hip).  A load: the uploaded encodings, the decoded points and verdicts, the
+  // running projective points, their live flags and affine forms, the verdict bytes.  An MSM: the scalars and
+  // indices, the sort's counters, offsets and lists, the fold's two partial arrays, the bit sums, the results
+  // (projective, live, affine) and the output bytes
+  S_G1T_IN, S_G1T_A, S_G1T_OK, S_G1T_CUR, S_G1T_LIVE, S_G1T_AFF, S_G1T_VERD,
+  S_G1M_IN, S_G1M_U32, S_G1M_PA, S_G1M_PB, S_G1M_U, S_G1M_RES, S_G1M_LIVE, S_G1M_AFF, S_G1M_OUT,
   NSLOT
 };
 
@@ -175,6 +181,16 @@ struct bls_ctx {
   std::vector<uint64_t> ctab_offs_h;
   bool ctab_loaded = false;
   uint64_t ctab_gen = 0;
+  // G1 point table (bls_g1_table_load, HBM resident): 32 window-major RegKey records per entry -- record
+  // w * g1t_cap + i is 2^(8w) T[i], REG_VALID on usable non-identity points -- and a state byte per entry (0 invalid,
+  // 1 point, 2 identity; the host copy checks an MSM's indices); g1t_checked: every load and append so far asked
+  // for the subgroup check; g1t_gen: bumped whenever the table is replaced; the MSM counters of bls_g1_table_stats
+  RegKey* g1t = nullptr;
+  uint8_t* g1t_stat = nullptr;
+  std::vector<uint8_t> g1t_stat_h;
+  size_t g1t_n = 0, g1t_cap = 0;
+  bool g1t_checked = false;
+  uint64_t g1t_gen = 0, g1t_msm_calls = 0, g1t_msm_entries = 0;
   Job* work_job = nullptr;  // the job whose bits batch bls_last_gather_work reports
   // test hook (bls_test_force_h2c_fallback): items whose hash_to_G2 is routed to k_h2c_fallback regardless of
   // the lane kernels' flags; null in every product use

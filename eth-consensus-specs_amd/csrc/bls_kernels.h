@@ -174,6 +174,28 @@ hipError_t launch_pt_msm(hipStream_t st, int group, const void* P, const uint8_t
 hipError_t launch_gt_final_exp(hipStream_t st, const Fp12* f, uint8_t* out576);
 hipError_t launch_gt_mul(hipStream_t st, const uint8_t* a, const uint8_t* b, uint8_t* out);
 
+// resident G1 table and its batched bucket MSM (bls_g1_table.hip, bls_g1_msm.h).  The table holds 32 window-major
+// RegKey records per entry (record w * cap + i = 2^(8w) T[i], REG_VALID on usable non-identity points) and a state
+// byte per entry (0 invalid, 1 point, 2 identity).
+// launch_g1_table_fill: entries first .. first + n from decoded points a / ok; cur (n G1P), live (n), aff (n G1A):
+// scratch; out_ok[i] = the encoding's verdict.
+hipError_t launch_g1_table_fill(hipStream_t st, const G1A* a, const int* ok, size_t n, RegKey* tab, size_t cap,
+                                size_t first, uint8_t* stat, G1P* cur, int* live, G1A* aff, uint8_t* out_ok);
+// what an MSM of B vectors over n items needs: bucket slots, the most entries, the fold's levels with the most runs
+// of each (its grids), the two partial arrays (G1P each) and the u32 scratch
+struct G1MsmPlan {
+  uint32_t slots;
+  size_t entries, u32_words, part[2], level_runs[8];
+  int levels;
+};
+G1MsmPlan g1_msm_plan(size_t n, size_t B);
+// out48[v] = sum_i [k32[v n + i]] T[idx[i]] (compressed), v < B; every idx names a valid entry; k32 16-byte aligned;
+// U: 8 B, res: B G1P, live: B, aff: B G1A; *d_entries: where the device leaves the number of bucket entries
+hipError_t launch_g1_table_msm(hipStream_t st, const G1MsmPlan& p, const RegKey* tab, uint32_t cap,
+                               const uint8_t* stat, const uint32_t* idx, uint32_t n, uint32_t B, const uint8_t* k32,
+                               uint32_t* scr, G1P* partA, G1P* partB, G1P* U, G1P* res, int* live, G1A* aff,
+                               uint8_t* out48, const uint32_t** d_entries);
+
 // wavefront-cooperative arithmetic (bls_wide.hip)
 hipError_t launch_wide_selftest(hipStream_t st, size_t nw, const uint8_t* be48, int* bad);
 // hash_to_G2 with one wave per message (msgs 32 B apart when offs is null); flag[i] = 1: recompute on the fallback;

@@ -315,6 +315,39 @@ int bls_point_neg(bls_ctx* ctx, int group, const uint8_t* p, uint8_t* out);
  * subgroup_check 0 = multiexp_unchecked (:280-282). */
 int bls_multi_exp(bls_ctx* ctx, int group, const uint8_t* pts, const uint8_t* scalars32, size_t n, int subgroup_check,
                   uint8_t* out);
+/* ---- resident G1 point table and its batched MSM (KZG g1_lincomb) ------- */
+/* The points a spec run multiplies again and again (KZG_SETUP_G1_LAGRANGE,
+ * KZG_SETUP_G1_MONOMIAL; specs/deneb/polynomial-commitments.md:266-286) are
+ * decoded once and kept in HBM, one table per context, with the window
+ * multiples 2^(8w) P (w = 0..31) of every entry as 128-byte affine records
+ * (4 KiB per entry), so that an MSM over them is additions only.
+ *
+ * bls_g1_table_load replaces the table with the n points of pts48 (decoded as
+ * bls_point_decode does, with or without the subgroup check); out_ok[i]
+ * (may be NULL) = 1 iff pts48[i] is a valid encoding (and, with
+ * subgroup_check, in G1).  An invalid entry keeps its index and is unusable:
+ * an MSM that names it returns 0.  The identity encoding is valid and
+ * contributes nothing.  bls_g1_table_append adds n entries at indices
+ * size .. size + n; existing indices stay.  At most 2^26 entries.
+ * bls_g1_table_generation is bumped whenever the table is replaced (appends
+ * keep it): a host-side bytes -> index map is valid only for the generation
+ * it was built on.  Return 1 or BLS_E_*. */
+int bls_g1_table_load(bls_ctx* ctx, const uint8_t* pts48, size_t n, int subgroup_check, uint8_t* out_ok);
+int bls_g1_table_append(bls_ctx* ctx, const uint8_t* pts48, size_t n, int subgroup_check, uint8_t* out_ok);
+size_t bls_g1_table_size(bls_ctx* ctx);
+uint64_t bls_g1_table_generation(bls_ctx* ctx);
+/* out48[v] = sum_i [k_{v,i}] T[idx[i]] for v < B: one shared list of n table
+ * indices and a B x n matrix of 32-byte big-endian scalars (row v at
+ * scalars32 + 32 n v), any 0 <= k < 2^256 taken as an integer multiple, as
+ * bls_multi_exp takes them.  An index may repeat.  Returns 1; 0 if an index
+ * names an invalid entry (the reference raises); BLS_E_NOREG without a table;
+ * BLS_E_ARG if n == 0 (the reference raises on an empty input), B == 0,
+ * B > 65,536, 32 B n >= 2^31 or an index is not below the table size. */
+int bls_g1_table_msm(bls_ctx* ctx, const uint32_t* idx, size_t n, const uint8_t* scalars32, size_t B, uint8_t* out48);
+/* Totals since the context was created: bls_g1_table_msm calls that ran and
+ * the bucket entries (non-zero digits of non-identity entries) they added.
+ * Returns 0. */
+int bls_g1_table_stats(bls_ctx* ctx, uint64_t* msm_calls, uint64_t* bucket_entries);
 /* GT.multi_pairing: prod_i e(P_i, Q_i) after the final exponentiation, as 576
  * bytes (six Fp2 coefficients c0..c5 of the w-basis, each c0||c1 big-endian;
  * GT one = byte 47 set).  n == 0 gives one. */
