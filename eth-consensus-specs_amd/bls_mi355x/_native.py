@@ -136,6 +136,7 @@ _SIGS = {
     "bls_test_final_check": (_ip, [_vp, _u8p, _sz, _ip, _vp]),
     "bls_test_hash_to_g2_wide": (_ip, [_vp, _u8p, _sz, _vp]),
     "bls_test_h2c_wide_stages": (_ip, [_vp, _u8p, _vp]),
+    "bls_test_rlc_msm": (_ip, [_vp, _u8p, _vp, _sz, ctypes.c_uint32, _vp]),
 }
 
 EXPORTS = tuple(_SIGS)

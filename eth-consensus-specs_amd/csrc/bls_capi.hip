@@ -157,7 +157,7 @@ static int fav_scratch(bls_ctx* ctx, const FavItems& it, FavScratch& S) {
   SCR(S_FLAG, NH, S.flag);
   SCR(S_RSC, B, S.rsc);
   SCR(S_MSMU, msm_scratch_u32(B), S.msmu);
-  SCR(S_MSMF, msm_scratch_fd(), S.msmf);
+  SCR(S_MSMF, msm_scratch_fd(B), S.msmf);
   SCR(S_HCF, h2c_scratch_fd(NH), S.hcf);
   SCR(S_RPJ, B, S.rpj);
   S.pstat = S.status;
@@ -190,21 +190,6 @@ static int fav_scratch(bls_ctx* ctx, const FavItems& it, FavScratch& S) {
     SCR(S_GAFF, fav_gather_aff_words(B), S.gaff);  // read per batch (gather_stage)
     SCR(S_GREDO, B, S.redo);
   }
-  return 0;
-}
-
-// the -G1 comb (bls_bisect.hip), built on first use: the MSM pairs' -w_b G1 and the bisection's -r_i G1
-static int ensure_comb(bls_ctx* ctx, hipStream_t st) {
-  if (ctx->comb) return 0;
-  G1A* tab = nullptr;
-  HIPCK(hipMalloc(&tab, neg_g1_comb_entries() * sizeof(G1A)));
-  hipError_t e = launch_neg_g1_comb_table(st, tab);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {  // never keep a table whose build did not complete
-    (void)hipFree(tab);
-    return fail(ctx, e, "launch_neg_g1_comb_table");
-  }
-  ctx->comb = tab;
   return 0;
 }
 

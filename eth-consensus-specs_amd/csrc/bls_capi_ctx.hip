@@ -104,6 +104,21 @@ hipError_t launch_pairs_decode(hipStream_t st, const uint8_t* d_in, size_t n, bo
   return e != hipSuccess ? e : launch_pt_decode(st, 2, d_in + 48 * n, n, subgroup ? 1 : 0, Q, ok2);
 }
 
+// the -G1 comb (bls_bisect.hip), built on first use: the MSM pairs' -w_b G1 and the bisection's -r_i G1
+int ensure_comb(bls_ctx* ctx, hipStream_t st) {
+  if (ctx->comb) return 0;
+  G1A* tab = nullptr;
+  HIPCK(hipMalloc(&tab, neg_g1_comb_entries() * sizeof(G1A)));
+  hipError_t e = launch_neg_g1_comb_table(st, tab);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {  // never keep a table whose build did not complete
+    (void)hipFree(tab);
+    return fail(ctx, e, "launch_neg_g1_comb_table");
+  }
+  ctx->comb = tab;
+  return 0;
+}
+
 // Copy n compressed keys, validate them on the device; returns 1 if all valid.
 int validate_pks(bls_ctx* ctx, const uint8_t* pks, size_t n, G1A** outA, int** outOk) {
   uint8_t* d_in;

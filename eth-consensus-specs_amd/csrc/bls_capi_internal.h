@@ -240,6 +240,7 @@ hipError_t launch_pairs_decode(hipStream_t st, const uint8_t* d_in, size_t n, bo
 hipError_t launch_miller_call(hipStream_t st, const G1A* P, const G2A* Q, size_t n, Fp12* f, size_t* nf,
                               const Fp2* qz);
 int stage_pairs(bls_ctx* ctx, const uint8_t* g1s48, const uint8_t* g2s96, size_t n, bool subgroup, G1A** P, G2A** Q);
+int ensure_comb(bls_ctx* ctx, hipStream_t st);  // ctx->comb, the -G1 comb (bls_bisect.hip), built on first use
 int host_seed(bls_ctx* ctx, uint8_t seed[32]);
 int nccl_fail(bls_ctx* c, ncclResult_t r, const char* where);
 void comm_fail_abort(bls_ctx* ctx);

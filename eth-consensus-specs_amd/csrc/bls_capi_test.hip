@@ -170,4 +170,43 @@ int bls_test_wide_selftest(bls_ctx* ctx, const uint8_t* in48, size_t nw, int32_t
   return 0;
 }
 
+// The 64 bit sums of the RLC signature MSM through launch_msm_upairs, the FAV batch's own stage (its scratch slots
+// too), compressed.  Both status arrays are the decode's verdicts.
+int bls_test_rlc_msm(bls_ctx* ctx, const uint8_t* sigs96, const uint64_t* scalars, size_t n, uint32_t run_len,
+                     uint8_t* out) {
+  API_ENTER(ctx);
+  if (!out || ((!sigs96 || !scalars) && n) || run_len > 16) return BLS_E_ARG;
+  hipStream_t st = ctx->j->stream;
+  uint8_t *d_in, *d_out;
+  uint64_t* rsc;
+  G2A *sig, *Q;
+  G1A* P;
+  int *dstat, *pok;
+  uint32_t* mu;
+  Fd* mf;
+  SCR(S_IN0, 96 * n, d_in);
+  SCR(S_RSC, n, rsc);
+  SCR(S_SIG, n, sig);
+  SCR(S_MSTAT, n, dstat);
+  SCR(S_MSMU, msm_scratch_u32(n), mu);
+  SCR(S_MSMF, msm_scratch_fd(n, run_len), mf);
+  SCR(S_RP, MSM_UPAIRS, P);
+  SCR(S_H, MSM_UPAIRS, Q);
+  SCR(S_STATUS, MSM_UPAIRS, pok);
+  SCR(S_IN2, 96 * MSM_UPAIRS, d_out);
+  CK(ensure_comb(ctx, st));
+  if (n) {
+    CK(h2d(ctx, d_in, sigs96, 96 * n));
+    CK(h2d(ctx, rsc, scalars, 8 * n));
+    HIPCK(launch_pt_decode(st, 2, d_in, n, 0, sig, dstat));
+    const int v = all_ok(ctx, dstat, n);
+    if (v <= 0) return v;
+  }
+  HIPCK(launch_msm_upairs(st, n, dstat, dstat, rsc, sig, mu, mf, ctx->comb, P, Q, pok, run_len));
+  hipLaunchKernelGGL(k_g2_compress_many, dim3(1), dim3(64), 0, st, (size_t)MSM_UPAIRS, Q, d_out);
+  HIPCK(hipGetLastError());
+  CK(d2h(ctx, out, d_out, 96 * MSM_UPAIRS));
+  return 1;
+}
+
 }  // extern "C"

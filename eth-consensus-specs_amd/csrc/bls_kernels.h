@@ -87,12 +87,15 @@ hipError_t launch_sig_decode_idx(hipStream_t st, size_t B, const uint8_t* msgs32
 hipError_t launch_sig_vm(hipStream_t st, size_t B, const int* gstat, int* status, const int* dstat, const G1P* apk_aff,
                          const G2A* sig, const uint64_t* rsc, G1P* rPj, G1A* rP);
 size_t msm_scratch_u32(size_t B);
-size_t msm_scratch_fd();
+size_t msm_scratch_fd(size_t B, uint32_t run_len = 0);
 // the 64 bit-sums U_b of S = sum_i r_i sigma_i = sum_b 2^b U_b as Miller pairs (-2^b G1, U_b) at P[0 .. 64),
-// Q[0 .. 64), ok[0 .. 64) = 1; comb: the bisection's -G1 comb (neg_g1_comb_entries() entries)
+// Q[0 .. 64), ok[0 .. 64) = 1; comb: the bisection's -G1 comb (neg_g1_comb_entries() entries); scr / pts:
+// msm_scratch_u32(B) words / msm_scratch_fd(B, run_len) slots.  run_len: entries per bucket run, 0 = chosen from B
+// (every batch; the test hook sets it to reach the run boundaries with few points)
 constexpr int MSM_UPAIRS = 64;
 hipError_t launch_msm_upairs(hipStream_t st, size_t B, const int* status, const int* status2, const uint64_t* rsc,
-                             const G2A* sig, uint32_t* scr, Fd* pts, const G1A* comb, G1A* P, G2A* Q, int* ok);
+                             const G2A* sig, uint32_t* scr, Fd* pts, const G1A* comb, G1A* P, G2A* Q, int* ok,
+                             uint32_t run_len = 0);
 // the same Miller values in two kernels (G2 lines, then f); L: miller_lines_u32(n) words of scratch
 constexpr int MILLER_NLINES = 68;  // 63 doublings + 5 additions (|x| = 0xd201000000010000)
 // Miller line records (k_miller_lines2 -> k_miller_acc4q): three Fp2 (l0, l2, l3), the line l0 + l2 (-x_P) v

@@ -2,13 +2,26 @@
 //
 // The 64-bit scalars split into 8 windows; the (item, window) pairs with a
 // nonzero digit d are counting-sorted into 8 x 255 buckets (atomic histogram,
-// one block-wide prefix scan, atomic scatter).  Seven launches:
-//   k_msm_count, k_msm_scan, k_msm_scatter   the sort
-//   k_msm_bucketc   each bucket's points summed in C strided chunks (C = 8 for
-//                   a C2 batch: one lane pair per chunk, ~5 mixed additions
-//                   each, 16,384 chunks = 512 waves, the point loads one step
-//                   ahead; fewer for smaller batches, msm_chunks), the chunks
-//                   then folded into the bucket sum B_{w,d} in LDS
+// one block-wide prefix scan, atomic scatter).  Eight launches:
+//   k_msm_count, k_msm_scan, k_msm_scatter   the sort; the scan also cuts each
+//                   bucket into runs of at most K = 16 entries (G2M_KMAX) and
+//                   leaves the runs' offsets
+//   k_msm_fold0     one lane per run, in the digit form (bls_g2_msm.h): the
+//                   accumulator starts as the run's first point, the rest are
+//                   complete mixed additions (g2q_add_aff) with the next
+//                   point's load in flight; a bucket's entries are cut evenly
+//                   (39 -> 13 + 13 + 13; ~96 waves for a C2 batch).  A bucket
+//                   of one run is written straight to the bucket sums
+//   k_msm_fold1     one lane per bucket: the run partials of a bucket with
+//                   more than one run folded into B_{w,d} (g2q_add_mem), the
+//                   identity written for a bucket without entries
+//                   (Before, the buckets were summed on lane pairs in the
+//                   packed form, 8 strided chunks per bucket from the
+//                   identity and a 3-level LDS fold: 512 waves, 152 SIMD-ms
+//                   per C2 batch against 55 now.  Below MSM_FOLD_MIN =
+//                   8,160 items that form stays, k_msm_bucketc with 4, 2 or
+//                   1 chunks in place of the two folds: a C3 or C5 batch has
+//                   its MSM on stream1's latency chain and gained nothing.)
 //   k_msm_usum      U_b = sum_{d : bit k of d} B_{w,d}  (b = 8w + k): one
 //                   wave per b, 32 lane pairs adding 4 bucket sums each, then a
 //                   5-level LDS tree (a 16-wave wide-arithmetic variant
@@ -31,7 +44,7 @@
 #include "bls_kernels.h"
 #include "bls_fp_inv.h"
 #include "bls_pp_lane.h"
-
+#include "bls_g2_msm.h"
 
 namespace bls {
 
@@ -49,33 +62,44 @@ __global__ void __launch_bounds__(256) k_msm_count(size_t B, const int* status, 
   if (d) atomicAdd(&cnt[w * 256 + d], 1u);
 }
 
-// off[b] = exclusive prefix of cnt; cur[b] = off[b] (scatter cursor); one 256-thread block, 8 buckets per thread
-__global__ void __launch_bounds__(256) k_msm_scan(const uint32_t* cnt, uint32_t* off, uint32_t* cur) {
+// off[b] = exclusive prefix of cnt; cur[b] = off[b] (scatter cursor); roff[b] = exclusive prefix of the buckets' run
+// counts ceil(cnt[b] / K); one 256-thread block, 8 buckets per thread
+__global__ void __launch_bounds__(256) k_msm_scan(const uint32_t* cnt, uint32_t K, uint32_t* off, uint32_t* cur,
+                                                  uint32_t* roff) {
   constexpr int PER = MSM_NB / 256;
-  __shared__ uint32_t part[256];
+  __shared__ uint32_t part[256], rpart[256];
   const int t = threadIdx.x;
-  uint32_t loc[PER], sum = 0;
+  uint32_t loc[PER], sum = 0, rsum = 0;
 #pragma unroll
   for (int i = 0; i < PER; i++) {
     loc[i] = cnt[t * PER + i];
     sum += loc[i];
+    rsum += g2m_nruns(loc[i], K);
   }
   part[t] = sum;
+  rpart[t] = rsum;
   __syncthreads();
   for (int d = 1; d < 256; d <<= 1) {  // inclusive Hillis-Steele scan of the per-thread sums
     const uint32_t v = t >= d ? part[t - d] : 0u;
+    const uint32_t rv = t >= d ? rpart[t - d] : 0u;
     __syncthreads();
     part[t] += v;
+    rpart[t] += rv;
     __syncthreads();
   }
-  uint32_t base = part[t] - sum;
+  uint32_t base = part[t] - sum, rbase = rpart[t] - rsum;
 #pragma unroll
   for (int i = 0; i < PER; i++) {
     off[t * PER + i] = base;
     cur[t * PER + i] = base;
+    roff[t * PER + i] = rbase;
     base += loc[i];
+    rbase += g2m_nruns(loc[i], K);
   }
-  if (t == 255) off[MSM_NB] = part[255];
+  if (t == 255) {
+    off[MSM_NB] = part[255];
+    roff[MSM_NB] = rpart[255];
+  }
 }
 
 __global__ void __launch_bounds__(256) k_msm_scatter(size_t B, const int* status, const int* status2,
@@ -89,18 +113,47 @@ __global__ void __launch_bounds__(256) k_msm_scatter(size_t B, const int* status
   if (d) lst[atomicAdd(&cur[w * 256 + d], 1u)] = (uint32_t)i;
 }
 
-constexpr int MSM_CMAX = 8;  // chunks per bucket, at most (msm_chunks)
-// chunks per bucket for a batch of B items: ~B / 255 points per bucket (8 windows of 255 nonzero digits); enough
-// chunks that a bucket's chain stays short on full batches, few enough that a C3- or C5-size batch is not mostly
-// fold tree and idle lanes (8 chunks of ~1 point each plus a 3-level fold at 2,048 items)
-static int msm_chunks(size_t B) {
-  const size_t per = B / 255;
-  return per >= 32 ? 8 : per >= 12 ? 4 : per >= 4 ? 2 : 1;
-}
 using P2 = PP<Fp2>;
 
+// ------------------------------------------------------ bucket sums (digit form) --
+// Level 0: lane r < roff[MSM_NB] folds run r (bls_g2_msm.h).  Its bucket b is the one with roff[b] <= r < roff[b + 1]
+// (bisection; an empty bucket shares its offset with its successor and is never found); the bucket's entries are cut
+// evenly over its roff[b + 1] - roff[b] runs.  A bucket of one run has its sum written straight to csum; else the
+// run's partial goes to part[r], so a bucket's partials lie together at part[roff[b] ..).  One lane per run, one
+// wave per SIMD, no cross-lane operation, no LDS, no private segment.
+__global__ void __launch_bounds__(64) k_msm_fold0(const uint32_t* off, const uint32_t* roff, const uint32_t* lst,
+                                                  const G2A* sig, G2SP* part, Fp* csum) {
+  const uint32_t r = blockIdx.x * 64 + threadIdx.x;
+  if (r >= roff[MSM_NB]) return;
+  uint32_t lo = 0, hi = MSM_NB;  // roff[lo] <= r < roff[hi]
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (roff[mid] <= r) lo = mid;
+    else hi = mid;
+  }
+  const uint32_t first = off[lo], runs = roff[lo + 1] - roff[lo];
+  const G2mRun g = g2m_run(off[lo + 1] - first, runs, r - roff[lo]);
+  const G2Q acc = g2m_fold_records(sig, lst + first + g.src, g.cnt);
+  g2m_store_run(part + r, csum + (size_t)lo * 6, runs == 1, acc);
+}
+
+// Level 1: lane b < MSM_NB finishes bucket b: the identity for a bucket without entries, nothing for a bucket of one
+// run (level 0 wrote its sum), else the fold of its run partials.
+__global__ void __launch_bounds__(64) k_msm_fold1(const uint32_t* roff, const G2SP* part, Fp* csum) {
+  const uint32_t b = blockIdx.x * 64 + threadIdx.x;
+  static_assert(MSM_NB % 64 == 0, "k_msm_fold1: whole waves");
+  const uint32_t r0 = roff[b], runs = roff[b + 1] - r0;
+  if (runs == 1) return;
+  Fp* o = csum + (size_t)b * 6;
+  if (!runs) {
+    g2m_store_identity(o);
+    return;
+  }
+  g2m_store_sum(o, g2m_fold_partials(part + r0, runs));
+}
+
 // ----------------------------------------------------------- lane form --
-// Bucket, U and weighted sums on lane pairs (bls_pp_lane.h pp2_*: complete
+// U and weighted sums on lane pairs (bls_pp_lane.h pp2_*: complete
 // projective formulas, each dependency level split between lanes 2k / 2k+1).
 namespace {
 // a point through LDS or HBM as six packed Fp: lane 0 of a pair writes x, y.c0, lane 1 y.c1, z
@@ -115,7 +168,21 @@ __device__ __forceinline__ P2 p2_load(const Fp* in) {
 }
 }  // namespace
 
-// chunk c of bucket b (lane pair (b, c)): csum[b C + c] = sum of the bucket's points k = off[b] + c + j C
+// Bucket sums of a batch below MSM_FOLD_MIN items, on lane pairs in the packed form.  There the MSM sits on
+// stream1's latency chain, and the run folds measured no gain (C3 the same, C5 -1 %: profiles/g2msm_ab.txt).
+// Measured were 1,024 and 2,048 items on this side and 10,000 and 125,000 on the other; nothing in between.  The
+// boundary is where the lane-pair form went to eight chunks, not a measured crossover.  (k_msm_scan's run offsets
+// are written here too and not read.)
+// chunks per bucket for such a batch of B items: ~B / 255 points per bucket; few enough that a C3- or C5-size batch
+// is not mostly fold tree and idle lanes
+constexpr size_t MSM_FOLD_MIN = 32 * 255;
+static int msm_chunks(size_t B) {
+  const size_t per = B / 255;
+  return per >= 12 ? 4 : per >= 4 ? 2 : 1;
+}
+
+// chunk c of bucket b (lane pair (b, c)): the sum of the bucket's points k = off[b] + c + j C from the identity, the
+// chunks then folded by a log2(C)-level LDS tree into csum[b]
 template <int MSM_C>
 __global__ void __launch_bounds__(64) k_msm_bucketc(const uint32_t* off, const uint32_t* lst, const G2A* sig,
                                                     Fp* csum) {
@@ -138,8 +205,6 @@ __global__ void __launch_bounds__(64) k_msm_bucketc(const uint32_t* off, const u
     li = k + 2 * MSM_C < end ? lst[k + 2 * MSM_C] : 0u;
     R = pp2_add_aff(R, cq.x, cq.y, hi);
   }
-  // the bucket's MSM_C chunk sums (lane pairs C b' .. C b' + C - 1 of this wave) folded by a log2(C)-level LDS tree, so the
-  // U sums read one point per bucket instead of re-adding its chunks once per set bit of the digit
   __shared__ Fp sm[32 * 6];
   const int lp = threadIdx.x >> 1;  // lane pair in the wave
 #pragma unroll 1
@@ -197,19 +262,38 @@ __global__ void __launch_bounds__(64) k_msm_upairs(const Fp* U, const G1A* comb,
   ok[b] = 1;
 }
 
-// Scratch: cnt[MSM_NB] | off[MSM_NB + 1] | cur[MSM_NB] (u32), lst[8 B] (u32);
-// points (packed Fp, 6 per point, in units of Fd slots): chunk sums [MSM_NB * MSM_CMAX] | U [64].
-size_t msm_scratch_u32(size_t B) { return (size_t)3 * MSM_NB + 1 + MSM_W * B; }
-size_t msm_scratch_fd() { return ((size_t)(MSM_NB * MSM_CMAX + 64) * 6 * sizeof(Fp) + sizeof(Fd) - 1) / sizeof(Fd); }
+// Scratch: cnt[MSM_NB] | off[MSM_NB + 1] | cur[MSM_NB] | roff[MSM_NB + 1] (u32), lst[8 B] (u32);
+// points (in units of Fd slots): bucket sums [MSM_NB] | U [64] (packed Fp, 6 per point) | run partials (G2SP), one per
+// run: at most 8 B / K full runs and one partly filled run per bucket.
+namespace {
+size_t msm_max_runs(size_t B, uint32_t K) { return MSM_W * B / K + MSM_NB; }
+// entries per run: G2M_KMAX for a batch of MSM_FOLD_MIN items or more, 0 (the lane-pair kernel) below; run_len != 0
+// (the test hook) asks for the run folds at that length whatever the size
+uint32_t msm_run_len(size_t B, uint32_t run_len) {
+  if (run_len) return run_len < G2M_KMAX ? run_len : G2M_KMAX;
+  return B >= MSM_FOLD_MIN ? G2M_KMAX : 0;
+}
+}  // namespace
+size_t msm_scratch_u32(size_t B) { return (size_t)4 * MSM_NB + 2 + MSM_W * B; }
+size_t msm_scratch_fd(size_t B, uint32_t run_len) {
+  const uint32_t K = msm_run_len(B, run_len);
+  const size_t bytes = (size_t)(MSM_NB + 64) * 6 * sizeof(Fp) + (K ? msm_max_runs(B, K) : 0) * sizeof(G2SP);
+  return (bytes + sizeof(Fd) - 1) / sizeof(Fd);
+}
 
 hipError_t launch_msm_upairs(hipStream_t st, size_t B, const int* status, const int* status2, const uint64_t* rsc,
-                             const G2A* sig, uint32_t* scr, Fd* pts, const G1A* comb, G1A* P, G2A* Q, int* ok) {
+                             const G2A* sig, uint32_t* scr, Fd* pts, const G1A* comb, G1A* P, G2A* Q, int* ok,
+                             uint32_t run_len) {
+  const uint32_t K = msm_run_len(B, run_len);
   uint32_t* cnt = scr;
   uint32_t* off = cnt + MSM_NB;
   uint32_t* cur = off + MSM_NB + 1;
-  uint32_t* lst = cur + MSM_NB;
+  uint32_t* roff = cur + MSM_NB;
+  uint32_t* lst = roff + MSM_NB + 1;
   Fp* csum = reinterpret_cast<Fp*>(pts);
-  Fp* U = csum + (size_t)MSM_NB * MSM_CMAX * 6;
+  Fp* U = csum + (size_t)MSM_NB * 6;
+  G2SP* part = reinterpret_cast<G2SP*>(U + 64 * 6);
+  static_assert(alignof(G2SP) <= alignof(Fp), "the run partials follow the packed points");
   hipError_t e = hipMemsetAsync(cnt, 0, MSM_NB * sizeof(uint32_t), st);
   if (e != hipSuccess) return e;
   const unsigned nb = (unsigned)((B * MSM_W + 255) / 256);
@@ -217,17 +301,24 @@ hipError_t launch_msm_upairs(hipStream_t st, size_t B, const int* status, const 
     hipLaunchKernelGGL(k_msm_count, dim3(nb), dim3(256), 0, st, B, status, status2, rsc, cnt);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(k_msm_scan, dim3(1), dim3(256), 0, st, cnt, off, cur);
+  hipLaunchKernelGGL(k_msm_scan, dim3(1), dim3(256), 0, st, cnt, K ? K : G2M_KMAX, off, cur, roff);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (B) {
     hipLaunchKernelGGL(k_msm_scatter, dim3(nb), dim3(256), 0, st, B, status, status2, rsc, cur, lst);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  switch (msm_chunks(B)) {
-    case 8: hipLaunchKernelGGL(k_msm_bucketc<8>, dim3(2 * MSM_NB * 8 / 64), dim3(64), 0, st, off, lst, sig, csum); break;
-    case 4: hipLaunchKernelGGL(k_msm_bucketc<4>, dim3(2 * MSM_NB * 4 / 64), dim3(64), 0, st, off, lst, sig, csum); break;
-    case 2: hipLaunchKernelGGL(k_msm_bucketc<2>, dim3(2 * MSM_NB * 2 / 64), dim3(64), 0, st, off, lst, sig, csum); break;
-    default: hipLaunchKernelGGL(k_msm_bucketc<1>, dim3(2 * MSM_NB / 64), dim3(64), 0, st, off, lst, sig, csum);
+  if (K) {
+    // the grid covers the most runs the batch can have; the lanes past roff[MSM_NB] leave at once
+    hipLaunchKernelGGL(k_msm_fold0, dim3((unsigned)((msm_max_runs(B, K) + 63) / 64)), dim3(64), 0, st, off, roff, lst,
+                       sig, part, csum);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_msm_fold1, dim3(MSM_NB / 64), dim3(64), 0, st, roff, part, csum);
+  } else {
+    switch (msm_chunks(B)) {
+      case 4: hipLaunchKernelGGL(k_msm_bucketc<4>, dim3(2 * MSM_NB * 4 / 64), dim3(64), 0, st, off, lst, sig, csum); break;
+      case 2: hipLaunchKernelGGL(k_msm_bucketc<2>, dim3(2 * MSM_NB * 2 / 64), dim3(64), 0, st, off, lst, sig, csum); break;
+      default: hipLaunchKernelGGL(k_msm_bucketc<1>, dim3(2 * MSM_NB / 64), dim3(64), 0, st, off, lst, sig, csum);
+    }
   }
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(k_msm_usum, dim3(64), dim3(2 * USUM_PAIRS), 0, st, csum, U);

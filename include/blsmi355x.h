@@ -532,6 +532,16 @@ int bls_test_final_check(bls_ctx* ctx, const uint8_t* f576, size_t n, int wide, 
  * integers < p); bad[w] = bitmask of differing forms, 0 when all agree. */
 int bls_test_wide_selftest(bls_ctx* ctx, const uint8_t* in48, size_t nw, int32_t* bad);
 
+/* bls_test_rlc_msm: the RLC batch check's signature MSM on n 96-byte signatures (decoded without subgroup checks;
+ * none may be the identity) and n 64-bit scalars, exactly as a FAV batch runs it (sort, bucket folds, bit sums, the
+ * affine conversion of the pairs): out holds the 64 bit sums U_b compressed (64 x 96 bytes, c0 00 .. for the
+ * identity), U_b = the sum of the sigma_i whose scalar has bit b.  The batch pairs them with -w_b G1, w_b = 2^b
+ * below bit 32 and 2^(b - 32) lambda above, so S = sum_b w_b U_b is left to the caller.  run_len: entries per bucket
+ * run, 0 = the batch's own choice for n items.  Uses the FAV batch's scratch: not between a batch's partial and
+ * finish calls.  1, or 0 on an invalid encoding. */
+int bls_test_rlc_msm(bls_ctx* ctx, const uint8_t* sigs96, const uint64_t* scalars, size_t n, uint32_t run_len,
+                     uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif
