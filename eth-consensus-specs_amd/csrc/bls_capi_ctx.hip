@@ -312,6 +312,9 @@ void bls_ctx_destroy(bls_ctx* ctx) {
   if (ctx->g1t) (void)hipFree(ctx->g1t);
   if (ctx->g1t_stat) (void)hipFree(ctx->g1t_stat);
   if (ctx->comb) (void)hipFree(ctx->comb);
+  if (ctx->kzg_dom) (void)hipFree(ctx->kzg_dom);
+  if (ctx->kzg_negtau) (void)hipFree(ctx->kzg_negtau);
+  if (ctx->kzg_idx) (void)hipFree(ctx->kzg_idx);
   if (ctx->force_fb) (void)hipFree(ctx->force_fb);
   if (ctx->pc_stage) (void)hipHostFree(ctx->pc_stage);
   delete ctx;

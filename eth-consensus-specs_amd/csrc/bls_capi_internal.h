@@ -65,6 +65,14 @@ enum Slot {
   // (projective, live, affine) and the output bytes
   S_G1T_IN, S_G1T_A, S_G1T_OK, S_G1T_CUR, S_G1T_LIVE, S_G1T_AFF, S_G1T_VERD,
   S_G1M_IN, S_G1M_U32, S_G1M_PA, S_G1M_PB, S_G1M_U, S_G1M_RES, S_G1M_LIVE, S_G1M_AFF, S_G1M_OUT,
+  // blob KZG (bls_capi_kzg.hip).  Blobs: the uploaded bytes, the elements, the lanes' prefix products, the per-blob
+  // verdicts, the z / y bytes, their elements and verdicts, the in-domain indices, the quotient rows.
+  // Verification: the encodings, the
+  // 3 n + 1 points, their verdicts, scalar rows, products and live flags, the sums' scratch and the two sums, the
+  // seed, the pairs, their Miller values, the per-item checks' selection and results
+  S_KB_BLOB, S_KB_F, S_KB_PRE, S_KB_OK, S_KB_Z32, S_KB_Y32, S_KB_ZF, S_KB_YF, S_KB_ZOK, S_KB_YOK, S_KB_HIT, S_KB_Q,
+  S_KB_ENC, S_KB_P, S_KB_POK, S_KB_K, S_KB_S, S_KB_LIVE, S_KB_J, S_KB_SUM, S_KB_SEED, S_KB_PP, S_KB_PQ, S_KB_FV,
+  S_KB_SEL, S_KB_RES,
   NSLOT
 };
 
@@ -191,6 +199,15 @@ struct bls_ctx {
   size_t g1t_n = 0, g1t_cap = 0;
   bool g1t_checked = false;
   uint64_t g1t_gen = 0, g1t_msm_calls = 0, g1t_msm_entries = 0;
+  // blob KZG (bls_capi_kzg.hip): the domain table omega^brp(i), filled on first use; the setup's -[tau] G2 and, with
+  // a Lagrange setup, the device list of its 4,096 table indices kzg_first + i and the G1 table generation it was
+  // made on (a commitment call after the table was replaced is refused, the committee table's rule)
+  Fr* kzg_dom = nullptr;
+  G2A* kzg_negtau = nullptr;
+  uint32_t* kzg_idx = nullptr;
+  bool kzg_set = false;
+  uint32_t kzg_first = 0, kzg_n = 0;
+  uint64_t kzg_gen = 0;
   Job* work_job = nullptr;  // the job whose bits batch bls_last_gather_work reports
   // test hook (bls_test_force_h2c_fallback): items whose hash_to_G2 is routed to k_h2c_fallback regardless of
   // the lane kernels' flags; null in every product use

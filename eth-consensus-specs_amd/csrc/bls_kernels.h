@@ -199,6 +199,34 @@ hipError_t launch_g1_table_msm(hipStream_t st, const G1MsmPlan& p, const RegKey*
                                uint32_t* scr, G1P* partA, G1P* partB, G1P* U, G1P* res, int* live, G1A* aff,
                                uint8_t* out48, const uint32_t** d_entries);
 
+// Deneb blob KZG on F_r (bls_kzg.hip; lane pieces bls_kzg_blob.h, field bls_fr.h).  Fr: 32 B, Montgomery form.
+// dom: the 4,096 domain entries omega^brp(i) (kzg_domain_bytes()); f: 4,096 elements per blob; ok[b] = every element
+// of blob b is < r (a failing element is stored as 0)
+struct Fr;
+size_t kzg_domain_bytes();
+hipError_t launch_fr_domain(hipStream_t st, Fr* dom);
+hipError_t launch_blob_decode(hipStream_t st, const uint8_t* blobs, size_t B, Fr* f, int* ok);
+// n 32-byte big-endian scalars: out[i] in Montgomery form and ok[i] = (scalar < r)
+hipError_t launch_fr_decode(hipStream_t st, const uint8_t* in32, size_t n, Fr* out, int* ok);
+// y[b] = p_b(z[b]) (also as 32 big-endian bytes), hit[b] = the domain index z[b] equals, or -1; ok nullable: a blob
+// with ok[b] = 0 gives y = 0; pre: 4,096 B elements of scratch (the lanes' prefix products)
+hipError_t launch_blob_eval(hipStream_t st, const Fr* dom, const Fr* f, const Fr* z, const int* ok, size_t B, Fr* pre,
+                            Fr* y, uint8_t* y32, int* hit);
+// q32: B rows of 4,096 32-byte scalars, the evaluation form of (p_b(X) - y[b]) / (X - z[b]); hit: launch_blob_eval's
+hipError_t launch_blob_quotient(hipStream_t st, const Fr* dom, const Fr* f, const Fr* z, const Fr* y, const int* hit,
+                                size_t B, Fr* pre, uint8_t* q32);
+// a verification batch's scalars and points: P holds the n decoded commitments, then the n proofs; the kernel adds
+// G1 at P[2 n] and the proofs again at P[2 n + 1 ..), and writes the 3 n + 1 scalar rows r_i | r_i z_i |
+// -sum r_i y_i | r_i (r_i: 128 bits from seed32 and i)
+hipError_t launch_kzg_rlc(hipStream_t st, const uint8_t* seed32, size_t n, const Fr* z, const Fr* y, G1A* P,
+                          uint8_t* k32);
+// P / Q[0 .. 2): (sums[1], negtau), (sums[0], G2)
+hipError_t launch_kzg_pairs(hipStream_t st, const G1J* sums, const G2A* negtau, G1A* P, G2A* Q);
+// P / Q[2 i], [2 i + 1]: (pi_i, negtau), (C_i + [z_i] pi_i - [y_i] G1, G2); CP: commitments, then proofs
+hipError_t launch_kzg_item_pairs(hipStream_t st, size_t n, const G1A* CP, const Fr* z, const Fr* y,
+                                 const G2A* negtau, G1A* P, G2A* Q);
+hipError_t launch_kzg_g2_neg(hipStream_t st, G2A* q);  // *q = -*q
+
 // wavefront-cooperative arithmetic (bls_wide.hip)
 hipError_t launch_wide_selftest(hipStream_t st, size_t nw, const uint8_t* be48, int* bad);
 // hash_to_G2 with one wave per message (msgs 32 B apart when offs is null); flag[i] = 1: recompute on the fallback;

@@ -348,6 +348,65 @@ int bls_g1_table_msm(bls_ctx* ctx, const uint32_t* idx, size_t n, const uint8_t*
  * the bucket entries (non-zero digits of non-identity entries) they added.
  * Returns 0. */
 int bls_g1_table_stats(bls_ctx* ctx, uint64_t* msm_calls, uint64_t* bucket_entries);
+/* ---- Deneb blob KZG on the device (specs/deneb/polynomial-commitments.md) -- */
+/* A blob is 4,096 field elements of 32 big-endian bytes (131,072 bytes), the
+ * evaluations of a polynomial p over the bit-reversed 4,096th roots of unity;
+ * z, y are 32-byte big-endian elements of F_r; commitments and proofs are
+ * 48-byte compressed G1 points.  The scalar-field arithmetic (range checks,
+ * barycentric evaluation, quotients, the batch's random linear combination)
+ * and the group side all run on the device.  Return 1 on success, 0 where the
+ * spec asserts (an element, z or y >= r; an invalid or non-G1 encoding) or a
+ * verification fails, BLS_E_* otherwise.
+ *
+ * The Fiat-Shamir challenge of the blob functions is an input (z32): it is
+ * one SHA-256 over a sequential transcript of 131,152 bytes -- the 16 bytes
+ * "FSBLOBVERIFY_V1_", the number 4,096 as 16 big-endian bytes, the blob, the
+ * 48-byte commitment -- taken as a big-endian integer mod r
+ * (compute_challenge, :247-264).  The host's SHA-256 does that in about
+ * 0.1 ms; bls_mi355x/kzg.py computes it.
+ *
+ * bls_kzg_setup: g2_tau96 = KZG_SETUP_G2_MONOMIAL[1] (subgroup-checked; kept
+ * negated).  lagrange_n = 0 sets up verification only; lagrange_n = 4096
+ * names entries lagrange_first .. lagrange_first + 4096 of the resident G1
+ * table (bls_g1_table_load / _append) as the bit-reversal-permuted
+ * KZG_SETUP_G1_LAGRANGE.  Returns 0 if tau's encoding or a named entry is
+ * invalid, BLS_E_NOREG without a table, BLS_E_ARG if the entries are out of
+ * range.  The setup remembers bls_g1_table_generation: after the table has
+ * been replaced, commitment and proof calls return BLS_E_ARG until
+ * bls_kzg_setup is called again (verification is unaffected).  A call that
+ * needs a setup (or its Lagrange entries) and finds none: BLS_E_NOREG. */
+int bls_kzg_setup(bls_ctx* ctx, const uint8_t* g2_tau96, uint32_t lagrange_first, uint32_t lagrange_n);
+/* y32[b] = p_b(z32[b]) (evaluate_polynomial_in_evaluation_form, :319-351) for
+ * B <= 1,024 blobs.  A z >= r returns 0.  out_ok[b] (may be NULL) = 1 iff
+ * every element of blob b is < r; otherwise y32[b] is zero.  Returns 1 iff
+ * every blob is ok.  Needs no setup. */
+int bls_kzg_eval_blobs(bls_ctx* ctx, const uint8_t* blobs, size_t B, const uint8_t* z32, uint8_t* y32,
+                       uint8_t* out_ok);
+/* out48[b] = blob_to_kzg_commitment(blob b): one row of the table MSM per
+ * blob, B <= 511.  out_ok as above; a bad blob's 48 bytes are zero. */
+int bls_kzg_blob_commitments(bls_ctx* ctx, const uint8_t* blobs, size_t B, uint8_t* out48, uint8_t* out_ok);
+/* compute_kzg_proof_impl (:508-541) for B <= 511 blobs: y32[b] = p_b(z_b) and
+ * proofs48[b] = the commitment to (p_b(X) - y_b) / (X - z_b), for z_b inside
+ * or outside the domain.  out_ok and the return value as above. */
+int bls_kzg_compute_proofs(bls_ctx* ctx, const uint8_t* blobs, size_t B, const uint8_t* z32, uint8_t* proofs48,
+                           uint8_t* y32, uint8_t* out_ok);
+/* verify_kzg_proof_batch (:412-463) as one check
+ *   e(sum r_i pi_i, -[tau] G2) e(sum r_i C_i + sum r_i z_i pi_i - (sum r_i y_i) G1, G2) == 1
+ * with independent 128-bit r_i derived from bls_host_seed (BLS_E_DEVICE when
+ * the entropy source fails): a batch with a false item passes with
+ * probability at most 2^-128.  n <= 65,536; n == 0 returns 1.  Returns 1 iff
+ * every item verifies.  An invalid encoding (the identity c0 00.. is valid)
+ * or a z or y >= r returns 0 without a pairing; out_item (may be NULL) then
+ * holds 0 for exactly the invalid items.  Otherwise out_item[i] = item i's
+ * own verdict: all ones after a passing batch, and after a failing one each
+ * item's own two-pair check. */
+int bls_kzg_verify_batch(bls_ctx* ctx, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32,
+                         const uint8_t* proofs48, size_t n, uint8_t* out_item);
+/* verify_blob_kzg_proof_batch (:589-614) given the challenges: y_b = p_b(z_b)
+ * on the device, then the batch check above on (C_b, z_b, y_b, pi_b).  A blob
+ * with an element >= r is an invalid item.  B <= 1,024. */
+int bls_kzg_verify_blob_batch(bls_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48,
+                              const uint8_t* proofs48, const uint8_t* z32, size_t B, uint8_t* out_item);
 /* GT.multi_pairing: prod_i e(P_i, Q_i) after the final exponentiation, as 576
  * bytes (six Fp2 coefficients c0..c5 of the w-basis, each c0||c1 big-endian;
  * GT one = byte 47 set).  n == 0 gives one. */
