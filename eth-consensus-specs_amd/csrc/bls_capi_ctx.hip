@@ -315,6 +315,9 @@ void bls_ctx_destroy(bls_ctx* ctx) {
   if (ctx->kzg_dom) (void)hipFree(ctx->kzg_dom);
   if (ctx->kzg_negtau) (void)hipFree(ctx->kzg_negtau);
   if (ctx->kzg_idx) (void)hipFree(ctx->kzg_idx);
+  if (ctx->kzc_tab) (void)hipFree(ctx->kzc_tab);
+  if (ctx->kzc_negtau64) (void)hipFree(ctx->kzc_negtau64);
+  if (ctx->kzc_idx) (void)hipFree(ctx->kzc_idx);
   if (ctx->force_fb) (void)hipFree(ctx->force_fb);
   if (ctx->pc_stage) (void)hipHostFree(ctx->pc_stage);
   delete ctx;

@@ -73,6 +73,16 @@ enum Slot {
   S_KB_BLOB, S_KB_F, S_KB_PRE, S_KB_OK, S_KB_Z32, S_KB_Y32, S_KB_ZF, S_KB_YF, S_KB_ZOK, S_KB_YOK, S_KB_HIT, S_KB_Q,
   S_KB_ENC, S_KB_P, S_KB_POK, S_KB_K, S_KB_S, S_KB_LIVE, S_KB_J, S_KB_SUM, S_KB_SEED, S_KB_PP, S_KB_PQ, S_KB_FV,
   S_KB_SEL, S_KB_RES,
+  // cell KZG (bls_capi_kzg_cells.hip).  Cells: the uploaded bytes, the index list and presence flags, the extended
+  // blobs (two buffers the recovery alternates between), the transform's intermediate, the coefficient form (kept
+  // after a call), the vanishing polynomial's values and inverses, the per-blob verdicts, the output bytes
+  S_KC_IN, S_KC_IDX, S_KC_PRES, S_KC_X, S_KC_Y, S_KC_T, S_KC_COEF, S_KC_ZD, S_KC_ZCI, S_KC_BAD, S_KC_OUT,
+  // ... verification: the encodings, the commitment and cell indices, the nc + 2 n + 1 points, their verdicts, the
+  // cells' verdicts and interpolation coefficients, the r_k, the column sums' partials and rows, the scalar rows,
+  // products and live flags, the sums' scratch and the two sums, the seed, the pairs, their Miller values, the
+  // per-item checks' selection and results, the interpolants' scalar rows and commitments
+  S_KC_ENC, S_KC_CIDX, S_KC_KIDX, S_KC_P, S_KC_POK, S_KC_COK, S_KC_CF, S_KC_RFR, S_KC_PART, S_KC_RLI, S_KC_K, S_KC_S,
+  S_KC_LIVE, S_KC_J, S_KC_SUM, S_KC_SEED, S_KC_PP, S_KC_PQ, S_KC_FV, S_KC_SEL, S_KC_RES, S_KC_ROWS, S_KC_I,
   NSLOT
 };
 
@@ -208,6 +218,14 @@ struct bls_ctx {
   bool kzg_set = false;
   uint32_t kzg_first = 0, kzg_n = 0;
   uint64_t kzg_gen = 0;
+  // cell KZG (bls_capi_kzg_cells.hip): the transform's tables w^i | 7^i | 7^-i, filled on first use
+  Fr* kzc_tab = nullptr;
+  // ... the cell setup's -[tau^64] G2, the device list of the 64 table indices of [tau^k] G1 and the G1 table
+  // generation it was made on (a verification after the table was replaced is refused, as for kzg_gen)
+  G2A* kzc_negtau64 = nullptr;
+  uint32_t* kzc_idx = nullptr;
+  bool kzc_set = false;
+  uint64_t kzc_gen = 0;
   Job* work_job = nullptr;  // the job whose bits batch bls_last_gather_work reports
   // test hook (bls_test_force_h2c_fallback): items whose hash_to_G2 is routed to k_h2c_fallback regardless of
   // the lane kernels' flags; null in every product use

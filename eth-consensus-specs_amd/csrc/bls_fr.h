@@ -1,5 +1,5 @@
 // The scalar field F_r of BLS12-381 (r = 0x73eda753...00000001, 255 bits) for device and host: the arithmetic under
-// the KZG blob functions (bls_kzg_blob.h) and, later, the cell functions' FFT.
+// the KZG blob functions (bls_kzg_blob.h) and the cell functions' transform (bls_fr_ntt.h).
 //
 // A value is a canonical residue (< r) in Montgomery form with R = 2^256, eight 32-bit little-endian limbs.  Products
 // are CIOS with 64-bit multiply-adds: a column t + a b + c of 32-bit operands is at most 2^64 - 1, so ordinary

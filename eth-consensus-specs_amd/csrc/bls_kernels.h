@@ -227,6 +227,45 @@ hipError_t launch_kzg_item_pairs(hipStream_t st, size_t n, const G1A* CP, const 
                                  const G2A* negtau, G1A* P, G2A* Q);
 hipError_t launch_kzg_g2_neg(hipStream_t st, G2A* q);  // *q = -*q
 
+// Fulu cell KZG on F_r (bls_kzg_cells.hip; the transform's pieces: bls_fr_ntt.h).  tab: w^i | 7^i | 7^-i, 8,192
+// entries each (ntt_tables_bytes()), w = 7^((r - 1) / 8192)
+size_t ntt_tables_bytes();
+hipError_t launch_ntt_tables(hipStream_t st, Fr* tab);
+// B transforms of 2^logn points (logn 12 or 13): blob b reads src + b src_stride and writes dst + b dst_stride (dst
+// may be src); tmp: B 2^logn entries.  flags: NTT_INV | NTT_SRC_BRP | NTT_DST_BRP; inputs from index `limit` on read
+// as zero (bls_fr_ntt.h)
+hipError_t launch_ntt(hipStream_t st, const Fr* W, uint32_t logn, uint32_t flags, uint32_t limit, size_t B,
+                      const Fr* src, size_t src_stride, Fr* tmp, Fr* dst, size_t dst_stride);
+// cells: B x n_present x 2,048 bytes, cell p of every blob at index idx[p] < 128; ext (B x 8,192, zeroed before) gets
+// the elements at 64 idx[p] + j, bad[b] (zeroed before) = 1 if an element of blob b is not below r
+hipError_t launch_cells_scatter(hipStream_t st, const uint8_t* cells, const uint32_t* idx, uint32_t n_present, size_t B,
+                                Fr* ext, int* bad);
+// present: 128 flags; zd[m] = Z(w^m) and zci[m] = 1 / Z(7 w^m), m < 128, Z the vanishing polynomial of the missing
+// cells' cosets
+hipError_t launch_cells_vanish(hipStream_t st, const uint8_t* present, const Fr* W, Fr* zd, Fr* zci);
+// dst[b][i] = src[b][brp ? brp13(i) : i] mul[i & mask], i < dst_n <= 8,192 (src: 8,192 per blob, dst: dst_n; dst may
+// be src when dst_n = 8,192 and brp is false)
+hipError_t launch_cells_pointwise(hipStream_t st, const Fr* src, Fr* dst, uint32_t dst_n, size_t B, bool brp,
+                                  const Fr* mul, uint32_t mask);
+hipError_t launch_fr_encode(hipStream_t st, const Fr* in, size_t n, uint8_t* out32);
+// n cells (2,048 bytes each) with cell indices kidx: coef[k] = the 64 coefficients of cell k's interpolation polynomial;
+// cok[k] = every element < r and kidx[k] < 128
+hipError_t launch_cells_interp(hipStream_t st, const uint8_t* cells, const uint32_t* kidx, size_t n, const Fr* W,
+                               Fr* coef, int* cok);
+// A cell batch's scalars and points.  P holds the nc decoded commitments, then the n proofs; the kernels add the
+// identity at P[nc + n] and the proofs again behind it, and write the nc + 2 n + 1 scalar rows: commitment i's sum of
+// the r_k of its items (cidx) | r_k h_k^64 | 0 | r_k (r_k: 128 bits from seed32 and k), and rli32, the 64 rows
+// -sum_k r_k c_{k,m}.  rfr: n elements; part: 64 cells_colsum_groups(n) elements
+size_t cells_colsum_groups(size_t n);
+hipError_t launch_cells_rlc(hipStream_t st, const uint8_t* seed32, size_t nc, size_t n, const uint32_t* cidx,
+                            const uint32_t* kidx, const Fr* W, const Fr* coef, Fr* rfr, Fr* part, G1A* P, uint8_t* k32,
+                            uint8_t* rli32);
+hipError_t launch_cells_put(hipStream_t st, const G1A* aff, const int* aff_live, G1A* S, int* live);  // *S, *live = ...
+// P / Q[2 k], [2 k + 1]: (pi_k, negtau64), (C_k - I_k + [h_k^64] pi_k, G2); CP: nc commitments, then n proofs
+hipError_t launch_cells_item_pairs(hipStream_t st, size_t nc, size_t n, const G1A* CP, const uint32_t* cidx,
+                                   const uint32_t* kidx, const G1A* I, const Fr* W, const G2A* negtau64, G1A* P,
+                                   G2A* Q);
+
 // wavefront-cooperative arithmetic (bls_wide.hip)
 hipError_t launch_wide_selftest(hipStream_t st, size_t nw, const uint8_t* be48, int* bad);
 // hash_to_G2 with one wave per message (msgs 32 B apart when offs is null); flag[i] = 1: recompute on the fallback;

@@ -407,6 +407,60 @@ int bls_kzg_verify_batch(bls_ctx* ctx, const uint8_t* commitments48, const uint8
  * with an element >= r is an invalid item.  B <= 1,024. */
 int bls_kzg_verify_blob_batch(bls_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48,
                               const uint8_t* proofs48, const uint8_t* z32, size_t B, uint8_t* out_item);
+/* ---- Fulu cell KZG on the device (specs/fulu/polynomial-commitments-sampling.md) -- */
+/* A cell is 64 field elements of 32 big-endian bytes (2,048 bytes); a blob
+ * extends to 128 cells: the evaluations of its polynomial over the
+ * bit-reversed 8,192nd roots of unity, so cells 0 .. 63 are the blob itself.
+ * The transforms are number-theoretic transforms over F_r on the device.
+ * Cell computation and recovery need no setup.
+ *
+ * bls_kzg_cells_setup: g2_tau64_96 = KZG_SETUP_G2_MONOMIAL[64] (subgroup-
+ * checked; kept negated); monomial_n = 64 names entries monomial_first ..
+ * monomial_first + 64 of the resident G1 table as KZG_SETUP_G1_MONOMIAL[0..64).
+ * Returns 0 if the encoding or a named entry is invalid, BLS_E_NOREG without a
+ * table, BLS_E_ARG if the entries are out of range or monomial_n is not 64.
+ * The setup remembers bls_g1_table_generation: after the table has been
+ * replaced, bls_kzg_verify_cells returns BLS_E_ARG until the setup is made
+ * again; without a setup it returns BLS_E_NOREG. */
+int bls_kzg_cells_setup(bls_ctx* ctx, const uint8_t* g2_tau64_96, uint32_t monomial_first, uint32_t monomial_n);
+/* verify_cell_kzg_proof_batch's check on n <= 8,192 items (n == 0 returns 1):
+ * item k is the cell cells + 2048 k with index cell_index[k] < 128, the proof
+ * proofs48 + 48 k and the commitment commitments48 + 48 commitment_index[k] of
+ * n_commitments <= 8,192 distinct ones (an index not below n_commitments:
+ * BLS_E_ARG).  One check of the universal verification equation
+ *   e(sum r_k pi_k, [tau^64] G2) ==
+ *   e(sum_i w_i C_i - sum_m s_m [tau^m] G1 + sum r_k h_k^64 pi_k, G2)
+ * with w_i the sum of the r_k of commitment i's items, s_m = sum r_k c_{k,m}
+ * over the coefficients c_k of cell k's interpolation polynomial (an inverse
+ * 64-point transform per cell) and h_k the cell's coset shift.  The r_k are
+ * independent 128-bit values derived from bls_host_seed as in
+ * bls_kzg_verify_batch, not powers of the spec's challenge: a batch with a
+ * false item passes with probability at most 2^-128.  Returns 1 iff every
+ * item verifies.  An invalid encoding (the identity is valid), a field
+ * element >= r or a cell index >= 128 returns 0 without a pairing; out_item
+ * (may be NULL) then holds 0 for exactly the invalid items.  Otherwise
+ * out_item[k] = item k's own verdict: all ones after a passing batch, and
+ * after a failing one each item's own two-pair check. */
+int bls_kzg_verify_cells(bls_ctx* ctx, const uint8_t* commitments48, size_t n_commitments,
+                         const uint32_t* commitment_index, const uint32_t* cell_index, const uint8_t* cells,
+                         const uint8_t* proofs48, size_t n, uint8_t* out_item);
+/*
+ * bls_kzg_compute_cells: cells[b] = compute_cells(blob b), 128 x 2,048 bytes
+ * per blob, for B <= 128 blobs: the inverse 4,096-point transform of the blob
+ * and the 8,192-point transform of its zero-padded coefficients.  out_ok[b]
+ * (may be NULL) = 1 iff every element of blob b is < r; otherwise blob b's
+ * cells are zero.  Returns 1 iff every blob is ok. */
+int bls_kzg_compute_cells(bls_ctx* ctx, const uint8_t* blobs, size_t B, uint8_t* cells, uint8_t* out_ok);
+/* The cells of recover_cells_and_kzg_proofs (recover_polynomialcoeff, then the
+ * extension above; the cell proofs are not computed) for B <= 128 blobs that
+ * share one list of present cells: cell_index, 64 <= n_present <= 128 strictly
+ * ascending indices below 128 (anything else: BLS_E_ARG); cells holds blob b's
+ * cell p (index cell_index[p]) at cells + 2048 (b n_present + p).  out_cells,
+ * out_ok and the return value as above, with every element of the given cells
+ * checked.  Given cells that lie on no polynomial of degree < 4,096 yield what
+ * the spec's algorithm yields on them. */
+int bls_kzg_recover_cells(bls_ctx* ctx, const uint32_t* cell_index, size_t n_present, const uint8_t* cells, size_t B,
+                          uint8_t* out_cells, uint8_t* out_ok);
 /* GT.multi_pairing: prod_i e(P_i, Q_i) after the final exponentiation, as 576
  * bytes (six Fp2 coefficients c0..c5 of the w-basis, each c0||c1 big-endian;
  * GT one = byte 47 set).  n == 0 gives one. */
