@@ -277,15 +277,18 @@ static int decode_stage(bls_ctx* ctx, const FavItems& it, const FavScratch& S, h
   return 0;
 }
 
-// the registry gather: the complete-formula kernel (k_fav_gather_q; 204 registers by the compiler's report, two
-// waves per SIMD), or with BLS_GATHER=affine (read per batch) affine additions sharing one inversion per level
-// (bls_gather_aff.hip: 42 % fewer VALU instructions per aggregate, 234 registers; C2 measured the same within
-// +-1 % over three A/Bs, profiles/r06_gather_ab.txt); aggregates with an exceptional pair are redone by the
-// complete formulas.  The gather is not free: 2,500 waves of a C2 batch, 30 % of the instructions the batch issues
-// and about a quarter of a C2 step (C2 / C4 = 1.39 per item, the work model's 1.38).  The affine
+// the registry gather: the complete-formula kernel (k_fav_gather_q: two keys of a lane summed first, then one
+// complete addition; 4 lanes per aggregate from 4,096 aggregates up, 16 from 1,024, else 64; 230 registers by the
+// compiler's report, two waves per SIMD), or with BLS_GATHER=affine (read per batch) affine additions sharing one
+// inversion per level (bls_gather_aff.hip: 42 % fewer VALU instructions per aggregate than the 16-lane kernel had
+// then, 234 registers; C2 measured the same within +-1 % over three A/Bs, profiles/r06_gather_ab.txt); aggregates
+// with an exceptional pair are redone by the complete formulas.  The gather is not free: it was 2,500 waves of a
+// C2 batch, 30 % of the instructions the batch issued and about a quarter of a C2 step (C2 / C4 =
+// 1.39 per item, the work model's 1.38).  The affine
 // A/B did not show that because its waves held their SIMDs alone, 28.5 % of the time waiting on HBM level lists
 // (~790 exclusive SIMD-ms, as much as it saved); cutting the complete kernel's own instructions by 15.8 % (one
-// reduction per output coordinate, bls_fq_g1.h) gained C2 3.1 % (profiles/g1dot_ab.txt).
+// reduction per output coordinate, bls_fq_g1.h) gained C2 3.1 % (profiles/g1dot_ab.txt), and by a further 20 %
+// (625 waves of 584,671 for 2,500 of 183,088: pair sums, four lanes) 3.3 % (profiles/gather_pairs_ab.txt).
 static int gather_stage(bls_ctx* ctx, const FavItems& it, const FavScratch& S, hipStream_t st) {
   Job& J = *ctx->j;
   const size_t B = it.B;

@@ -1,7 +1,9 @@
 // Complete projective G1 additions (Renes-Costello-Batina alg. 7 / 8 / 9, a = 0,
 // b3 = 12) in the redundant digit form of bls_fq.h, for the registry gather
 // (k_fav_gather_q, bls_kernels.hip), the r_i apk_i chain (bls_g1_endo.h) and the
-// segmented and workgroup G1 sums.
+// segmented and workgroup G1 sums; and the sum of two affine points in
+// homogeneous coordinates (g1q_add_aff2: 7 digit products, incomplete, x2 != x3),
+// which the registry gather forms of every two keys of a lane before one g1q_add.
 #pragma once
 #include "bls_fqb.h"
 
@@ -33,9 +35,11 @@ namespace bls {
 // g1q_add_aff is in N form (< 2p, 29-bit digits).  Outputs: every coordinate in
 // N form except g1q_dbl's X3 = 2 w u (< 4p, digits <= 2^29), so the outputs are
 // inputs again and every loop over them closes.
+// g1q_add_aff2 takes two affine points in N form and returns N form: an operand
+// of g1q_add.
 // The host tests (tests/test_hostcheck.py::test_fq_gather_formulas,
-// tests/test_g1dot_cpu.py) run these formulas with the 128-bit column checks of
-// bls_fq.h.
+// tests/test_g1dot_cpu.py, tests/test_g1pair_cpu.py) run these formulas with the
+// 128-bit column checks of bls_fq.h.
 struct G1Q {
   Fq x, y, z;
 };
@@ -113,6 +117,47 @@ BLS_HD G1Q g1q_add(const G1Q& p, const G1Q& q) {
   r.y = out(dot2(t1p, z3, y3, t0p));
   r.z = out(dot2(z3, t4, t0p, t3));
   r.x = out(dot2(t3, t1p, t4, ny3));
+  return r;
+}
+
+// whether the plain product a b fits its columns with these bounds
+template <class A, class B>
+constexpr bool mul_fits() {
+  return fqb_detail::columns_fit(A::dig, fqb_detail::top(A::val), B::dig, fqb_detail::top(B::val));
+}
+
+// sum of two affine points (x2, y2), (x3, y3) in N form with x2 != x3, in homogeneous coordinates without an
+// inversion (the chord through both, denominators cleared by H^3):
+//   H = x3 - x2,  R = y3 - y2,  HH = H^2,  HHH = H HH,  V = x2 HH,  W = R^2 - HHH - 2 V
+//   X = H W,  Y = R (V - W) - y2 HHH = R (V - W) + HHH (K - y2),  Z = HHH
+// two squarings, five digit products (Y is one dot2) and six reductions, against the 22 products and 16
+// reductions of two mixed additions; the registry gather adds the result to its accumulator with g1q_add.
+// INCOMPLETE: for x2 == x3 the result is (0 : -R^3 : 0) -- the identity -- when y3 == -y2 and (0 : 0 : 0), not
+// a point, when the two points are equal.  The caller guards x2 != x3 (k_fav_gather_q: such a pair takes two
+// g1q_add_aff).  Outputs in N form: operands of g1q_add.
+BLS_HD G1Q g1q_add_aff2(const Fq& x2_, const Fq& y2_, const Fq& x3_, const Fq& y3_) {
+  using namespace g1q_detail;
+  const FqN x2{x2_}, y2{y2_}, x3{x3_}, y3{y3_};
+  const auto Hr = x3 - x2;
+  const auto Rr = y3 - y2;
+  const auto H = norm(Hr);
+  const auto R = norm(Rr);
+  const FqN HH = sqr(H);
+  const FqN HHH = H * HH;
+  const FqN V = x2 * HH;
+  const auto Wr = sqr(R) - (HHH + V + V);
+  const auto W = norm(Wr);
+  const auto VWr = V - W;
+  const auto VW = norm(VWr);
+  const auto ny2 = neg(y2);  // unnormalised: its partner HHH is
+  static_assert(!mul_fits<decltype(Hr), decltype(Hr)>(), "H needs no normalisation in H^2");
+  static_assert(!mul_fits<decltype(Rr), decltype(Rr)>(), "R needs no normalisation in R^2");
+  static_assert(!mul_fits<decltype(H), decltype(Wr)>(), "W needs no normalisation in X");
+  static_assert(!dot2_fits<decltype(R), decltype(VWr), FqN, decltype(ny2)>(), "V - W needs no normalisation in Y");
+  G1Q r;
+  r.x = out(H * W);
+  r.y = out(dot2(R, VW, HHH, ny2));
+  r.z = out(HHH);
   return r;
 }
 

@@ -147,7 +147,8 @@ hipError_t launch_bits_expand(hipStream_t st, size_t B, int mode, const uint32_t
   return hipGetLastError();
 }
 
-// lanes per aggregate as launch_fav_gather chooses them: 16 from 1,024 aggregates up, else 64
+// lanes per aggregate: 16 from 1,024 aggregates up, else 64 (launch_fav_gather goes on to 4 lanes for full batches
+// with its pair-first loop; this kernel keeps one key per step)
 hipError_t launch_fav_gather_bits(hipStream_t st, const uint32_t* list, const BitsItem* items, size_t B,
                                   const RegKey* reg, uint32_t reg_n, const uint32_t* comm_ids,
                                   const uint64_t* comm_offs, const G1P* csum, G1P* apk, int* status,

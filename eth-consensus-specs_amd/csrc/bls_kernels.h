@@ -21,6 +21,8 @@ hipError_t launch_percall_pairs(hipStream_t st, const G1A* keys, const int* key_
 hipError_t launch_hash_many(hipStream_t st, const uint8_t* msgs, const uint64_t* offs, size_t n, const uint8_t* dst, uint32_t dst_len, G2A* out);
 hipError_t launch_sign_many(hipStream_t st, const uint8_t* sks, const uint8_t* msgs, const uint64_t* offs, size_t n, uint8_t* out, int* ok);
 hipError_t launch_sk_to_pk_many(hipStream_t st, const uint8_t* sks, size_t n, uint8_t* out, int* ok);
+// the registry gather (k_fav_gather_q: two keys per step, the pair summed first): 4 lanes per aggregate from 4,096
+// aggregates up, 16 from 1,024 up, else 64
 hipError_t launch_fav_gather(hipStream_t st, const uint32_t* idx, const uint64_t* offs, size_t B, const RegKey* reg, uint32_t reg_n, G1P* apk, int* status);
 // the affine gather (bls_gather_aff.hip) for batches of >= 4,096 aggregates: scratch of fav_gather_aff_words(B) u32,
 // redo[B] (1 = recompute with launch_fav_gather_redo, the complete-formula kernel on the flagged aggregates only)

@@ -271,19 +271,30 @@ __global__ void __launch_bounds__(64) k_sk_to_pk_many(const uint8_t* sks32, size
 
 // ------------------------------------------------------- FAV batch path --
 // Aggregate pubkeys: L lanes per aggregate, 64 / L aggregates per workgroup.
-// Each lane adds its strided share of the registry points with the complete
-// projective mixed addition (Renes-Costello-Batina alg. 8, 11 products, no
-// exceptional cases), then an LDS tree of complete additions (alg. 7), all in
-// the redundant digit form (bls_fq_g1.h: g1q_add_aff, g1q_add).  The tree costs
-// log2(L) full additions of the whole wave, so for mainnet-sized committees
-// L = 16 (32 mixed additions per lane + 4 tree levels) beats 64 lanes (8 + 6
-// levels: the tree was ~45 % of the wave's time).
+// Each lane adds its strided share of the registry points two keys at a time:
+// the pair's sum in homogeneous coordinates (g1q_add_aff2: 7 products, x2 != x3)
+// goes into the accumulator with one complete addition (Renes-Costello-Batina
+// alg. 7), against two complete mixed additions (alg. 8, 11 products each).  A
+// pair with equal x (a repeated key, a key beside its negation) and an odd tail
+// key take the mixed additions, so no sum depends on the incomplete formula.
+// Then an LDS tree of complete additions, all in the redundant digit form
+// (bls_fq_g1.h).  The tree costs log2(L) full additions of the whole wave: for a
+// 512-key committee L = 4 is 64 pair steps per lane + 2 levels (full batches,
+// bound by total work), L = 16 is 16 + 4 levels (a shorter chain for the C3
+// epoch), L = 64 is 4 + 6 levels (a few aggregates).
+constexpr size_t GATHER_FULL_MIN = 4096;  // aggregates from which a batch is bound by total work
+constexpr int GATHER_FULL_LANES = 4;      // lanes per aggregate of such a batch (launch_fav_gather)
 template <int L>
-__global__ void __launch_bounds__(64) k_fav_gather_q(const uint32_t* idx, const uint64_t* offs, size_t B,
-                                                     const RegKey* reg, uint32_t reg_n, G1P* apk, int* status,
-                                                     const int* only) {
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
+k_fav_gather_q(const uint32_t* idx, const uint64_t* offs, size_t B, const RegKey* reg, uint32_t reg_n, G1P* apk,
+               int* status, const int* only) {
   constexpr int IPW = 64 / L;
-  __shared__ G1Q sh[64];
+  // one LDS block: in the loop a lane's slot (slot[w][lane], 12 x 16 B per lane) for the next pair's records while
+  // the complete addition runs, or for the two keys of a pair on the complete path; then the tree's sums
+  __shared__ uint4 lds[12 * 64];
+  static_assert(sizeof(G1Q) * 64 <= sizeof(lds), "the tree's sums fit the block");
+  G1Q* const sh = reinterpret_cast<G1Q*>(lds);
+  uint4* const slot = lds + threadIdx.x;
   __shared__ int bad[IPW];
   const int sub = (int)threadIdx.x / L, ln = (int)threadIdx.x % L;
   const size_t b = (size_t)blockIdx.x * IPW + sub;
@@ -306,41 +317,87 @@ __global__ void __launch_bounds__(64) k_fav_gather_q(const uint32_t* idx, const 
   if (mine) {
     lo = offs[b];
     hi = offs[b + 1];
-    // software pipeline: the record of key j + L and the index of key j + 2L are in flight while key j is added
-    // (an out-of-range index reads record 0 and is flagged; every load is unconditional)
+    // Two keys per step: the keys at j and j + L are a pair, summed first (g1q_add_aff2) and added to the
+    // accumulator with one g1q_add.  Software pipeline: the two records of the pair at j + 2L, j + 3L and the
+    // indices of the pair after it are in flight while this pair is added (an out-of-range or absent index reads
+    // record 0; every load is unconditional).
     uint64_t j = lo + ln;
-    uint32_t k1 = j < hi ? idx[j] : 0u;
-    const uint32_t* rw = reinterpret_cast<const uint32_t*>(reg + (k1 < reg_n ? k1 : 0u));
-    uint4 r[6];
+    uint32_t ka = j < hi ? idx[j] : 0u, kb = j + L < hi ? idx[j + L] : 0u;
+    uint4 ra[6], rb[6];
+    {
+      const uint4* pa = reinterpret_cast<const uint4*>(reg + (ka < reg_n ? ka : 0u));
+      const uint4* pb = reinterpret_cast<const uint4*>(reg + (kb < reg_n ? kb : 0u));
 #pragma unroll
-    for (int w = 0; w < 6; ++w) r[w] = reinterpret_cast<const uint4*>(rw)[w];
-    uint32_t k2 = j + L < hi ? idx[j + L] : 0u;
+      for (int w = 0; w < 6; ++w) ra[w] = pa[w], rb[w] = pb[w];
+    }
+    uint32_t na = j + 2 * L < hi ? idx[j + 2 * L] : 0u, nb = j + 3 * L < hi ? idx[j + 3 * L] : 0u;
 #pragma unroll 1
-    for (; j < hi; j += L) {
-      uint4 cr[6];
-#pragma unroll
-      for (int w = 0; w < 6; ++w) cr[w] = r[w];
-      const uint32_t ck = k1;
-      k1 = k2;
-      const uint4* nr = reinterpret_cast<const uint4*>(reg + (k1 < reg_n ? k1 : 0u));
-#pragma unroll
-      for (int w = 0; w < 6; ++w) r[w] = nr[w];
-      k2 = j + 2 * L < hi ? idx[j + 2 * L] : 0u;
-      Fp x, y;
+    for (; j < hi; j += 2 * L) {
+      Fp xa, ya, xb, yb;
 #pragma unroll
       for (int w = 0; w < 3; ++w) {
-        reinterpret_cast<uint4*>(x.l)[w] = cr[w];
-        reinterpret_cast<uint4*>(y.l)[w] = cr[3 + w];
+        reinterpret_cast<uint4*>(xa.l)[w] = ra[w];
+        reinterpret_cast<uint4*>(ya.l)[w] = ra[3 + w];
+        reinterpret_cast<uint4*>(xb.l)[w] = rb[w];
+        reinterpret_cast<uint4*>(yb.l)[w] = rb[3 + w];
       }
-      if (ck >= reg_n || !(x.l[11] & REG_VALID)) {
-        mybad = 1;
+      const uint32_t cka = ka, ckb = kb;
+      const bool hb = j + L < hi;  // an odd tail has no second key
+      ka = na;
+      kb = nb;
+      const uint4* pa = reinterpret_cast<const uint4*>(reg + (ka < reg_n ? ka : 0u));
+      const uint4* pb = reinterpret_cast<const uint4*>(reg + (kb < reg_n ? kb : 0u));
+#pragma unroll
+      for (int w = 0; w < 6; ++w) ra[w] = pa[w], rb[w] = pb[w];
+      na = j + 4 * L < hi ? idx[j + 4 * L] : 0u;
+      nb = j + 5 * L < hi ? idx[j + 5 * L] : 0u;
+      const bool oka = cka < reg_n && (xa.l[11] & REG_VALID);
+      const bool okb = ckb < reg_n && (xb.l[11] & REG_VALID);
+      xa.l[11] &= ~REG_VALID;
+      xb.l[11] &= ~REG_VALID;
+      uint32_t dx = 0;  // canonical x limbs: equal for a repeated key and for a key beside its negation
+#pragma unroll
+      for (int w = 0; w < 12; ++w) dx |= xa.l[w] ^ xb.l[w];
+      if (!oka || (hb && !okb)) {
+        mybad = 1;  // the pair is skipped: the aggregate's status is 0 whatever its sum
+      } else if (hb && dx != 0) {
+        const G1Q s = g1q_add_aff2(fq_unpack(xa), fq_unpack(ya), fq_unpack(xb), fq_unpack(yb));
+        // the next pair's records, in flight behind the pair sum, have arrived: they wait in the slot while the
+        // complete addition runs (beside its operands they do not fit 256 registers)
+#pragma unroll
+        for (int w = 0; w < 6; ++w) slot[64 * w] = ra[w], slot[64 * (6 + w)] = rb[w];
+        asm volatile("" ::: "memory");
+        acc = g1q_add(acc, s);
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int w = 0; w < 6; ++w) ra[w] = slot[64 * w], rb[w] = slot[64 * (6 + w)];
       } else {
-        x.l[11] &= ~REG_VALID;
-        acc = g1q_add_aff(acc, fq_unpack(x), fq_unpack(y));
+        // the complete path, one key after the other: an odd tail key (hb false), or a pair with equal x, which
+        // the pair sum cannot add.  Rare, so both keys wait in LDS and one rolled loop adds them: held in
+        // registers beside the records in flight they would cost the whole kernel its second wave per SIMD.
+#pragma unroll
+        for (int w = 0; w < 3; ++w) {
+          slot[64 * w] = reinterpret_cast<const uint4*>(xa.l)[w];
+          slot[64 * (3 + w)] = reinterpret_cast<const uint4*>(ya.l)[w];
+          slot[64 * (6 + w)] = reinterpret_cast<const uint4*>(xb.l)[w];
+          slot[64 * (9 + w)] = reinterpret_cast<const uint4*>(yb.l)[w];
+        }
+        asm volatile("" ::: "memory");  // the loop below reads the slot, not these registers
+#pragma unroll 1
+        for (int t = 0; t < (hb ? 2 : 1); ++t) {
+          Fp x, y;
+#pragma unroll
+          for (int w = 0; w < 3; ++w) {
+            reinterpret_cast<uint4*>(x.l)[w] = slot[64 * (6 * t + w)];
+            reinterpret_cast<uint4*>(y.l)[w] = slot[64 * (6 * t + 3 + w)];
+          }
+          acc = g1q_add_aff(acc, fq_unpack(x), fq_unpack(y));
+        }
       }
     }
   }
   if (mybad) atomicOr(&bad[sub], 1);
+  __syncthreads();  // every lane is past its slot
   sh[threadIdx.x] = acc;
   __syncthreads();
 #pragma unroll 1
@@ -585,10 +642,16 @@ hipError_t launch_sk_to_pk_many(hipStream_t st, const uint8_t* sks, size_t n, ui
 hipError_t launch_fav_gather(hipStream_t st, const uint32_t* idx, const uint64_t* offs, size_t B, const RegKey* reg,
                              uint32_t reg_n, G1P* apk, int* status) {
   if (!B) return hipSuccess;
-  // lanes per aggregate: 16 from 1,024 aggregates up (C2 and the C3 epoch of 2,048: 32 mixed additions per lane and
-  // a 4-level tree beat 8 + 6 levels of 64 lanes -- C3 +4 %, profiles/r03u_inv_gather_ab.txt), else 64 (a few
-  // aggregates spread over more lanes: shorter chains)
-  if (B >= 1024)
+  // lanes per aggregate: GATHER_FULL_LANES from GATHER_FULL_MIN aggregates up (a full batch is bound by total
+  // work: 16 aggregates per workgroup, 64 pair steps per lane for a 512-key committee and a 2-level tree, of which
+  // 3 of 8 lane-additions are useful against 15 of 64 at 16 lanes; C2 +3.3 % where the pair-first loop at 16 lanes
+  // gave +0.9 %, 2 and 8 lanes inside 4's range -- profiles/gather_pairs_ab.txt), 16 from 1,024 aggregates up (the
+  // C3 epoch of 2,048: a shorter chain, and a 4-level tree beat 6 levels of 64 lanes -- C3 +4 %,
+  // profiles/r03u_inv_gather_ab.txt), else 64 (a few aggregates spread over more lanes: shorter chains)
+  if (B >= GATHER_FULL_MIN)
+    LAUNCH(k_fav_gather_q<GATHER_FULL_LANES>, (unsigned)((B + 64 / GATHER_FULL_LANES - 1) / (64 / GATHER_FULL_LANES)),
+           64, st, idx, offs, B, reg, reg_n, apk, status, (const int*)nullptr);
+  else if (B >= 1024)
     LAUNCH(k_fav_gather_q<16>, (unsigned)((B + 3) / 4), 64, st, idx, offs, B, reg, reg_n, apk, status,
            (const int*)nullptr);
   else
