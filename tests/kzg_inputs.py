@@ -137,6 +137,48 @@ def known_answers():
             KnownAnswer([rng.randrange(R) for _ in range(66)]))
 
 
+@functools.lru_cache(maxsize=None)
+def linear_answers():
+    """four polynomials p = a0 + a1 X as (a0, a1, commitment, proof): p(X) - p(z) = a1 (X - z), so the proof is
+    [a1] M[0] whatever z is, and y = a0 + a1 z"""
+    rng = random.Random(0x11EA12)
+    out = []
+    for _ in range(4):
+        a0, a1 = rng.randrange(1, R), rng.randrange(1, R)
+        out.append((a0, a1, commit_monomial([a0, a1]), commit_monomial([a1])))
+    return tuple(out)
+
+
+CUBIC_Z = (0x5EED, DOMAIN[15], 0, 3, DOMAIN[4095], R - 2, 1 << 200, 0xC0FFEE)
+
+
+@functools.lru_cache(maxsize=None)
+def cubic_openings():
+    """eight openings (C, z, y, proof) of the degree-3 known answer, three oracle multiplications each"""
+    a = known_answers()[1]
+    return tuple((a.commitment, z) + a.open(z) for z in CUBIC_Z)
+
+
+@functools.lru_cache(maxsize=None)
+def batch_items(n: int, seed: int = 0xBA7C4):
+    """n valid items (C, z, y, proof) at no oracle cost per item: the four linear polynomials in turn, each item
+    with a random z of its own; every 16th item (i = 15 mod 16) one of the eight cubic openings; every 37th
+    (i = 36 mod 37) the zero polynomial with the identity as commitment and as proof"""
+    rng = random.Random(seed)
+    lin, cub = linear_answers(), cubic_openings()
+    out = []
+    for i in range(n):
+        z = rng.randrange(R)
+        if i % 37 == 36:
+            out.append((IDENTITY48, z, 0, IDENTITY48))
+        elif i % 16 == 15:
+            out.append(cub[(i // 16) % len(cub)])
+        else:
+            a0, a1, c, proof = lin[i % 4]
+            out.append((c, z, (a0 + a1 * z) % R, proof))
+    return tuple(out)
+
+
 def random_blob(seed: int) -> list:
     rng = random.Random(seed)
     return [rng.randrange(R) for _ in range(N)]

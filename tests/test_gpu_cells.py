@@ -1,8 +1,9 @@
 """GPU tests of the device cell KZG functions (bls_kzg_cells_setup, bls_kzg_verify_cells, bls_kzg_compute_cells,
 bls_kzg_recover_cells; bls_mi355x.kzg_cells): batch verification of known answers from the monomial setup with every
 way of being wrong and per-item verdicts, cells against the Python FFT of cell_inputs.py, recovery against the full
-extension and against the restatement of the spec's algorithm, and the setup's lifecycle.  The trusted setup comes
-from the fixture tests/golden/trusted_setup.json only."""
+extension and against the restatement of the spec's algorithm, the setup's lifecycle, verification at the sizes where
+the call changes shape (seam_sizes.py) and the Python calls' chunking.  The trusted setup comes from the fixture
+tests/golden/trusted_setup.json only."""
 import ctypes
 import functools
 
@@ -11,6 +12,7 @@ import pytest
 
 import cell_inputs as C
 import kzg_inputs as K
+import seam_sizes as Z
 from dispatch_edge_inputs import non_subgroup_g1
 from oracle import bls_oracle as O
 
@@ -324,3 +326,93 @@ def test_setup_lifecycle(mods):
         assert (rc, ok) == (1, [1]) and raw == b"".join(C.blobs()[2][3])
     finally:
         ctx.close()
+
+
+# ---- verification at size (tests/seam_sizes.py) --------------------------------------------------------------------
+def deduped(items):
+    """verify_raw's arguments for batch_items' four commitments as the table and every item's index into it"""
+    distinct = [a.commitment for a in C.cell_answers()]
+    assert len(set(distinct)) == Z.CELL_COMMITMENTS == len(distinct)
+    return dict(commitments=distinct, index=[distinct.index(i[0]) for i in items])
+
+
+def off_by_one(item, element):
+    cell = bytearray(item[2])
+    cell[32 * element + 31] ^= 1
+    return (item[0], item[1], bytes(cell), item[3])
+
+
+@pytest.mark.parametrize("n", Z.CELLS_VALID)
+def test_valid_batches_across_the_sum_switches(S, n):
+    """four commitments for n = 2,043 | 2,044 cells (the first sum's nc + n + 1 points pass 2,048: k_g1_sum_q, then
+    the two-pass sum) and n = 2,048 | 2,049 (the second sum's n points pass it)"""
+    items = C.batch_items(n)
+    assert verify_raw(S.ctx, items, **deduped(items)) == (1, [1] * n)
+    assert verify_raw(S.ctx, items, want_items=False, **deduped(items))[0] == 1
+
+
+@pytest.mark.parametrize("n", Z.CELLS_FAILING)
+def test_failing_batches_across_the_msm_chunks(S, n):
+    """n = 511, 512, 1,023: the per-item path's interpolant commitments come from one table MSM of 511 rows, from
+    511 + 1 and from 511 + 511 + 1, each chunk copied behind the one before.  One element of the cells at 0, 510,
+    511 and n - 1 (those below n) is off by one: the call and the Python call name exactly those."""
+    items = C.batch_items(n)
+    bad = sorted({p % n for p in Z.CELLS_BAD_AT if p < n})
+    assert len(bad) == {511: 2, 512: 3, 1023: 4}[n]
+    for p in bad:
+        items[p] = off_by_one(items[p], (7 * p + 3) % 64)
+    want = [k not in bad for k in range(n)]
+    assert verify_raw(S.ctx, items, **deduped(items)) == (0, [int(v) for v in want])
+    assert verify_raw(S.ctx, items, want_items=False, **deduped(items))[0] == 0
+    assert S.verify_cell_kzg_proof_items(*unzip(items)) == want
+    # one bad cell alone, the first chunk's last row: a later chunk written over the first one's rows, or left out of
+    # its own, would call good items bad (at n = 512 the positions above are exactly the rows that would hit)
+    items = C.batch_items(n)
+    lone = Z.KZC_MSM_ROWS - 1
+    items[lone] = off_by_one(items[lone], 1)
+    assert verify_raw(S.ctx, items, **deduped(items)) == (0, [int(k != lone) for k in range(n)])
+
+
+def test_offsetting_errors_a_lane_stride_apart_fail(S):
+    """items 7 and 7 + 256 name one cell index with proofs pi + D and pi' - D: the errors cancel exactly when both
+    items get the same r.  This test fails if k_cells_rlc's r_k repeats with its 256 lanes, which no valid batch
+    and no batch with a single bad item can show."""
+    n = 300
+    i, j = 7, 7 + Z.RLC_LANES
+    a, b = C.cell_answers()[2], C.cell_answers()[3]
+    ia, ib = a.item(5), b.item(5)
+    items = C.batch_items(n)
+    items[i] = (ia[0], 5, ia[2], add_g1(ia[3], 11))
+    items[j] = (ib[0], 5, ib[2], add_g1(ib[3], -11))
+    want = [k not in (i, j) for k in range(n)]
+    assert verify_raw(S.ctx, items, **deduped(items)) == (0, [int(v) for v in want])
+    assert S.verify_cell_kzg_proof_items(*unzip(items)) == want
+    assert S.verify_cell_kzg_proof_batch(*unzip(items)) is False
+
+
+def test_more_cells_than_a_call_takes_is_an_argument_error(S):
+    item = C.cell_answers()[1].item(3)
+    n = Z.KZC_ITEMS_MAX + 1
+    assert verify_raw(S.ctx, [item] * n, commitments=[item[0]], index=[0] * n)[0] == BLS_E_ARG
+    assert verify_raw(S.ctx, [item] * 2, commitments=[item[0]], index=[0] * 2) == (1, [1, 1])  # the same form, accepted
+
+
+# ---- the Python calls' chunking -------------------------------------------------------------------------------------
+def test_list_calls_join_their_chunks_in_order(S, mods, monkeypatch):
+    """ITEMS_MAX = 5 and BLOBS_MAX = 2 in place of 8,192 and 128: twelve cells and five blobs go through every
+    list-taking call in three chunks; the outputs are the known answers in order, and a bad cell of the last chunk is
+    named at its position in the whole list"""
+    monkeypatch.setattr(mods.kc, "ITEMS_MAX", 5)
+    monkeypatch.setattr(mods.kc, "BLOBS_MAX", 2)
+    items = C.batch_items(12)
+    assert S.verify_cell_kzg_proof_items(*unzip(items)) == [True] * 12
+    for bad in (11, 10, 5):
+        spoiled = items[:bad] + [off_by_one(items[bad], 40)] + items[bad + 1:]
+        assert S.verify_cell_kzg_proof_items(*unzip(spoiled)) == [k != bad for k in range(12)], bad
+    blobs = C.blobs()
+    order = [0, 1, 2, 0, 2]  # chunks (random, zero), (degree 65, random), (degree 65)
+    assert S.compute_cells_batch([blobs[b][1] for b in order]) == [blobs[b][3] for b in order]
+    missing = set(C.missing_sets()["random_17"])
+    idx = [k for k in range(128) if k not in missing]
+    given = [[blobs[b][3][k] for k in idx] for b in order]
+    assert S.recover_cells_batch(idx, given) == [blobs[b][3] for b in order]

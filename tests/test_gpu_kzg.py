@@ -1,7 +1,8 @@
 """GPU tests of the device blob KZG functions (bls_kzg_*; bls_mi355x.kzg): evaluations against Horner and the
 restatement of kzg_inputs.py, commitments and proofs against known answers from the monomial setup and against the
 table MSM on the restatement's quotient, verification with every way of being wrong, batches with per-item verdicts,
-and the setup's lifecycle.  The blob size is the spec's 4,096 elements; no call has more than 6 blobs."""
+the setup's lifecycle, verification batches at the sizes where the call changes shape (seam_sizes.py) and the Python
+calls' chunking.  The blob size is the spec's 4,096 elements; no call has more than 6 blobs."""
 import ctypes
 import hashlib
 import random
@@ -10,6 +11,7 @@ import numpy as np
 import pytest
 
 import kzg_inputs as K
+import seam_sizes as Z
 from dispatch_edge_inputs import non_subgroup_g1
 from oracle import bls_oracle as O
 
@@ -328,3 +330,91 @@ def test_setup_lifecycle(items, ka, mods):
         assert s.first == 0 and s.blob_to_kzg_commitment(ka[1].blob) == ka[1].commitment
     finally:
         ctx.close()
+
+
+# ---- verification at size (tests/seam_sizes.py) --------------------------------------------------------------------
+def spoil_y(it):
+    return (it[0], it[1], (it[2] + 1) % R, it[3])
+
+
+def shift_proof(it, k):
+    """the item with its proof moved by [k] G1"""
+    return (it[0], it[1], it[2], O.g1_compress(O.g1_add(O.g1_decompress(it[3]), O.g1_mul(O.G1_GEN, k % R))))
+
+
+@pytest.mark.parametrize("n", Z.KZG_VALID)
+def test_valid_batches_across_the_stride_and_the_sum_switches(S, n):
+    """n = 256, 257 (a lane of k_kzg_rlc takes a second item), 1,023, 1,024 (the first sum's 2 n + 1 points pass
+    2,048: k_g1_sum_q, then the two-pass sum), 2,048, 2,049 (the second sum's n points pass it); linear, cubic and
+    zero polynomials mixed, a z of its own per item"""
+    items = list(K.batch_items(n))
+    assert verify_batch(S.ctx, items) == (1, [1] * n)
+    assert verify_batch(S.ctx, items, want_items=False)[0] == 1
+
+
+@pytest.mark.parametrize("n", Z.KZG_FAILING)
+def test_failing_batches_name_exactly_the_bad_items(S, n):
+    """y spoiled at 0, 255, 256 and n - 1: the batch check fails and the per-item path (2 n pairs on the two-pair
+    kernel, n selected final checks) names those (three for n = 257, whose last item is 256) and no other"""
+    items = list(K.batch_items(n))
+    bad = sorted({p % n for p in Z.KZG_BAD_AT})
+    assert bad == {257: [0, 255, 256], 1024: [0, 255, 256, 1023]}[n]
+    for p in bad:
+        items[p] = spoil_y(items[p])
+    assert verify_batch(S.ctx, items) == (0, [int(i not in bad) for i in range(n)])
+    assert verify_batch(S.ctx, items, want_items=False)[0] == 0
+
+
+@pytest.mark.parametrize("distance", [Z.RLC_LANES, 64])
+def test_offsetting_errors_across_the_lane_stride_fail(S, distance):
+    """Items i and i + distance carry the same (C, z, y) with proofs pi + D and pi - D: their errors r_i D (tau - z)
+    and -r_j D (tau - z) cancel exactly when r_i = r_j.  This test fails if r_i repeats with the lane count of
+    k_kzg_rlc (i taken mod 256 in the hash input, or item i + 256 given lane i's scalar row): every valid batch
+    and every batch with one bad item would still get its right verdict.  Distance 64 is the same for a wave."""
+    n = 300
+    i, j = 3, 3 + distance
+    items = list(K.batch_items(n))
+    base = items[i]
+    assert base[3] != ID and i % 16 != 15
+    items[i], items[j] = shift_proof(base, 11), shift_proof(base, -11)
+    assert verify_batch(S.ctx, items) == (0, [int(k not in (i, j)) for k in range(n)])
+    assert verify_batch(S.ctx, items, want_items=False)[0] == 0
+    items[j] = base
+    assert verify_batch(S.ctx, items) == (0, [int(k != i) for k in range(n)])
+
+
+# ---- the Python calls' chunking -------------------------------------------------------------------------------------
+def test_list_calls_join_their_chunks_in_order(S, ka, items, mods, monkeypatch):
+    """MSM_ROWS_MAX = 2, BLOBS_MAX = 2 and ITEMS_MAX = 4 in place of 511, 1,024 and 65,536: five blobs and eleven
+    items go through every list-taking call in three chunks each; the outputs are the known answers in order, and a
+    bad item of the last chunk is named at its position in the whole list"""
+    kzg = mods.kzg
+    monkeypatch.setattr(kzg, "MSM_ROWS_MAX", 2)
+    monkeypatch.setattr(kzg, "BLOBS_MAX", 2)
+    monkeypatch.setattr(kzg, "ITEMS_MAX", 4)
+    answers = [ka[1], ka[0], None, ka[2], ka[1]]  # None: the zero blob
+    blobs = [a.blob if a else ZERO_BLOB for a in answers]
+    zs = [0x5EED, 77, 5, 99, K.DOMAIN[15]]
+    opened = [a.open(z) if a else (0, ID) for a, z in zip(answers, zs)]
+    s0 = mods.batch.g1_table_stats(S.ctx)
+    assert S.blob_to_kzg_commitments(blobs) == [a.commitment if a else ID for a in answers]
+    s1 = mods.batch.g1_table_stats(S.ctx)
+    assert s1[0] - s0[0] == 3  # chunks of 2, 2 and 1 rows
+    assert S.compute_kzg_proofs(blobs, zs) == [(proof, fe(y)) for y, proof in opened]
+    assert mods.batch.g1_table_stats(S.ctx)[0] - s1[0] == 3
+    assert S.evaluate_blobs(blobs, zs) == [fe(y) for y, _ in opened]
+    # eleven items in chunks of 4, 4 and 3
+    eleven = (items + items)[:11]
+    cols = [list(c) for c in zip(*eleven)]
+    assert S.verify_kzg_proof_items(*cols) == [True] * 11
+    for bad in (9, 10, 4):
+        spoiled = eleven[:bad] + [spoil_y(eleven[bad])] + eleven[bad + 1:]
+        assert S.verify_kzg_proof_items(*[list(c) for c in zip(*spoiled)]) == [k != bad for k in range(11)], bad
+    # five blobs with their commitments and proofs at the Fiat-Shamir challenge, in chunks of 2, 2 and 1
+    cms = [a.commitment if a else ID for a in answers]
+    proofs = [a.open(kzg.compute_challenge(b, c))[1] if a else ID for a, b, c in zip(answers, blobs, cms)]
+    assert S.verify_blob_kzg_proof_items(blobs, cms, proofs) == [True] * 5
+    assert S.verify_blob_kzg_proof_batch(blobs, cms, proofs) is True
+    for bad in (4, 2):
+        wrong = proofs[:bad] + [ka[1].commitment] + proofs[bad + 1:]
+        assert S.verify_blob_kzg_proof_items(blobs, cms, wrong) == [k != bad for k in range(5)], bad
