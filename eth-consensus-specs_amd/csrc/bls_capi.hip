@@ -884,6 +884,15 @@ static int job_submit(bls_ctx* ctx, const FavItems& it, bool exchange) {
   HIPCK(hipEventRecord(J.ev[EV_PARTIAL], J.stream));
   J.partial_pending = true;
   if (exchange) {
+    if (B) {
+      // the own check runs only if the combined one fails, at any later time (read_own): it gets a copy of the
+      // product in a slot of its own, right behind it in stream order.  S_FPART is rewritten by every per-call
+      // product (AggregateVerify, AggregateVerify batches, the pairing checks) on job 0 meanwhile, and a passing
+      // one there would make a failing shard keep every status
+      Fp12* own_f;
+      SCR(S_OWN_F, 1, own_f);
+      HIPCK(hipMemcpyAsync(own_f, f, sizeof(Fp12), hipMemcpyDeviceToDevice, J.stream));
+    }
     CK(enqueue_comm_check(ctx));
     J.own_pending = false;
     J.own_state = B ? -2 : 1;  // -2: computed on demand (read_own); an empty shard passes
@@ -912,7 +921,7 @@ static int job_submit_exchange(bls_ctx* ctx, int arg_error, const FavItems& it) 
 // no batch submitted on this job, or another batch prepared on the slot since).
 static int read_own(bls_ctx* ctx, int* state) {
   Job& J = *ctx->j;
-  if (J.own_state == -2) CK(enqueue_own_check(ctx, (const Fp12*)J.buf[S_FPART].p, false));
+  if (J.own_state == -2) CK(enqueue_own_check(ctx, (const Fp12*)J.buf[S_OWN_F].p, false));
   if (J.own_pending) {
     HIPCK(hipEventSynchronize(J.ev[EV_OWN]));
     J.own_state = J.h_own[0] ? 1 : 0;

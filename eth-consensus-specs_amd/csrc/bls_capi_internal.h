@@ -41,6 +41,9 @@ enum Slot {
   // partial and finish calls, and fav_bisect reads them back)
   S_PC_P,
   S_OWN,  // the job's own final check (enqueue_own_check)
+  // the job's product again, for an own check that runs on demand (job_submit with the device exchange, read_own):
+  // S_FPART is every per-call product's slot too, and such calls may come between the submit and the finish
+  S_OWN_F,
   S_GAFF, S_GREDO,  // the affine gather's level lists and redo flags (bls_gather_aff.hip)
   S_COMM, S_CV,  // the all-gathered partials of all ranks and their check's verdict (enqueue_comm_check)
   // shared-message batches (FavItems::msg_id): the pair arrays' status and G1 side (M + MSM_UPAIRS; the

@@ -524,7 +524,22 @@ int bls_fav_batch_finish_dev(bls_ctx* ctx, int batch_ok, uint8_t* d_out);
  *   finish:  verdicts into d_out, enqueued on the job's stream without a host
  *            wait -- a failing batch's bisection runs there on the device (no
  *            host round trip per round) while the host checks the next job;
- *            bls_d2h / bls_sync wait for it */
+ *            bls_d2h / bls_sync wait for it
+ * Other calls on the context between a job's submit and its finish -- the
+ * per-call verifications, aggregation, the pairing and curve calls, the G1
+ * table, signing roots, the KZG calls, bls_registry_append -- run on job 0
+ * and leave a submitted batch's verdicts unchanged, on job 0 as on every
+ * other job, with or without a communicator.  The exceptions replace what the
+ * slot holds:
+ *   - the host-buffer batch calls (bls_fav_batch_indexed, _indexed_shared,
+ *     _keys, _committee_bits, bls_verify_batch_*, bls_deposits_verify)
+ *     prepare their batch on job 0: a batch submitted there before is
+ *     replaced.  bls_fav_job_check_own(ctx, 0) is then BLS_E_ARG, and
+ *     bls_fav_job_finish_dev(ctx, 0, 0, d_out) bisects the replacing batch
+ *     from its root and writes that batch's verdicts.
+ *   - bls_committees_load and the registry calls wait for the device before
+ *     they replace (or grow) a table, so the pending batch's verdicts are
+ *     unchanged: a submitted batch has read the tables it was submitted on. */
 int bls_fav_job_submit_dev(bls_ctx* ctx, int job, const uint32_t* d_idx, const uint64_t* d_offsets, size_t B,
                            const uint8_t* d_msgs32, const uint8_t* d_sigs96, const uint8_t* seed32);
 /* The shared-message form of submit (bls_fav_batch_indexed_shared): d_idx,
