@@ -130,6 +130,10 @@ _SIGS = {
     "bls_kzg_verify_cells": (_ip, [_vp, _u8p, _sz, _vp, _vp, _u8p, _u8p, _sz, _vp]),
     "bls_kzg_compute_cells": (_ip, [_vp, _u8p, _sz, _vp, _vp]),
     "bls_kzg_recover_cells": (_ip, [_vp, _vp, _sz, _u8p, _sz, _vp, _vp]),
+    "bls_g1_fft": (_ip, [_vp, _u8p, _sz, _sz, _ip, _vp]),
+    "bls_kzg_cell_proofs_setup": (_ip, [_vp, ctypes.c_uint32, ctypes.c_uint32]),
+    "bls_kzg_compute_cells_and_proofs": (_ip, [_vp, _u8p, _sz, _vp, _vp, _vp]),
+    "bls_kzg_recover_cells_and_proofs": (_ip, [_vp, _vp, _sz, _u8p, _sz, _vp, _vp, _vp]),
     "bls_multi_pairing": (_ip, [_vp, _u8p, _u8p, _sz, _ip, _vp]),
     "bls_gt_mul": (_ip, [_vp, _u8p, _u8p, _vp]),
     "bls_pairing_check_ex": (_ip, [_vp, _u8p, _u8p, _sz, _ip]),

@@ -644,6 +644,7 @@ class G1Table:
     def __init__(self, ctx: _native.Context | None = None):
         self.ctx = ctx or _native.context()
         self._index: dict[bytes, int] = {}
+        self._last: dict[bytes, int] = {}  # the highest index of every point: ``run_of`` past repeated points
         self._ok = np.zeros(0, dtype=np.uint8)
         self._gen = None
         self.checked = False
@@ -668,6 +669,7 @@ class G1Table:
         raw = buf.tobytes()
         for i in range(len(raw) // 48):
             self._index.setdefault(raw[48 * i: 48 * i + 48], first + i)
+            self._last[raw[48 * i: 48 * i + 48]] = first + i
         self._ok = np.concatenate([self._ok[:first], ok])
 
     def load(self, points48, subgroup_check: bool = False) -> np.ndarray:
@@ -677,7 +679,7 @@ class G1Table:
         n = buf.size // 48
         ok = np.zeros(n, dtype=np.uint8)
         c = self.ctx
-        self._index, self._gen, self._ok = {}, None, np.zeros(0, dtype=np.uint8)
+        self._index, self._last, self._gen, self._ok = {}, {}, None, np.zeros(0, dtype=np.uint8)
         c.check(c.lib.bls_g1_table_load(c.h, buf.tobytes(), n, 1 if subgroup_check else 0, _ptr(ok)))
         self.checked = bool(subgroup_check)
         self._remember(buf, 0, ok)
@@ -708,6 +710,17 @@ class G1Table:
                 return None
             out[i] = k
         return out
+
+    def run_of(self, points) -> int | None:
+        """the index at which the points lie in the table as one consecutive run, by their first or by their last
+        occurrences (a list appended behind a shorter copy of its head is found by the latter); else None"""
+        if not self._current() or not len(points):
+            return None
+        for where in (self._index, self._last):
+            idx = [where.get(bytes(p)) for p in points]
+            if idx[0] is not None and idx == list(range(idx[0], idx[0] + len(idx))):
+                return idx[0]
+        return None
 
     def usable(self, i: int) -> bool:
         return self._current() and 0 <= i < self._ok.size and bool(self._ok[i])
@@ -769,6 +782,30 @@ def g1_table_stats(ctx=None) -> tuple[int, int, int]:
     calls, entries = ctypes.c_uint64(), ctypes.c_uint64()
     c.check(c.lib.bls_g1_table_stats(c.h, ctypes.byref(calls), ctypes.byref(entries)))
     return int(calls.value), int(entries.value), int(getattr(c, "g1_decode_hits", 0))
+
+
+def g1_fft(points, inverse: bool = False, ctx=None):
+    """The radix-2 transform over G1 on the device (``bls_g1_fft``): out[k] = sum_i [w_n^(i k)] points[i], w_n the
+    n-th root of unity of the cell functions' domain, in natural order on both sides; ``inverse`` takes w_n^-1 and
+    includes 1 / n.  ``points``: n = 2^k (2 <= n <= 4,096) 48-byte encodings, the identity allowed anywhere -- or a
+    list of such lists of one length, transformed in one call, which returns a list of lists.  Raises ValueError on
+    a size the call does not take and on an encoding that is invalid or not in G1."""
+    c = ctx or _native.context()
+    rows = list(points)
+    nested = bool(rows) and not isinstance(rows[0], (bytes, bytearray, memoryview))
+    vecs = [[bytes(p) for p in v] for v in rows] if nested else [[bytes(p) for p in rows]]
+    n = len(vecs[0])
+    if any(len(v) != n for v in vecs) or any(len(p) != 48 for v in vecs for p in v):
+        raise ValueError("need vectors of one length of 48-byte G1 encodings")
+    out = ctypes.create_string_buffer(max(48 * n * len(vecs), 1))
+    rc = c.lib.bls_g1_fft(c.h, b"".join(b"".join(v) for v in vecs), n, len(vecs), 1 if inverse else 0, out)
+    if rc == _native.BLS_E_ARG:
+        raise ValueError("the G1 transform takes n = 2^k points, 2 <= n <= 4096, and at least one vector")
+    if c.check(rc) != 1:
+        raise ValueError("invalid G1 point encoding")
+    raw = out.raw
+    res = [[raw[48 * (n * v + i): 48 * (n * v + i + 1)] for i in range(n)] for v in range(len(vecs))]
+    return res if nested else res[0]
 
 
 def fallback_stats(ctx=None) -> tuple[int, int]:

@@ -1,5 +1,6 @@
 """Fulu cell KZG on the device (``bls_kzg_cells_setup``, ``bls_kzg_verify_cells``, ``bls_kzg_compute_cells``,
-``bls_kzg_recover_cells``; specs/fulu/polynomial-commitments-sampling.md).
+``bls_kzg_recover_cells``, ``bls_kzg_cell_proofs_setup``, ``bls_kzg_compute_cells_and_proofs``,
+``bls_kzg_recover_cells_and_proofs``; specs/fulu/polynomial-commitments-sampling.md).
 
 ``CellSetup`` puts what cell verification needs on the device -- ``[tau^k] G1`` for k < 64 as entries of the
 context's resident G1 table, ``[tau^64] G2`` negated -- and carries ``verify_cell_kzg_proof_batch``, ``compute_cells``
@@ -9,9 +10,14 @@ cell_setup)`` puts them in place of a spec module's own (``uninstall_cells`` res
 
 The transforms (inverse 4,096 and forward / inverse 8,192 points over F_r, one inverse 64-point transform per
 verified cell), the range checks, the batch's random linear combination and the group side run on the device.  The
-cell proofs (``compute_cells_and_kzg_proofs`` and the proofs of ``recover_cells_and_kzg_proofs``) are not computed
-here; the batch check draws its own coefficients, so ``compute_verify_cell_kzg_proof_batch_challenge`` is neither
-provided nor used.
+batch check draws its own coefficients, so ``compute_verify_cell_kzg_proof_batch_challenge`` is neither provided nor
+used.
+
+``CellProofSetup`` names the 4,096 monomial points ``[tau^i] G1`` in the context's G1 table and carries
+``compute_cells_and_kzg_proofs`` and ``recover_cells_and_kzg_proofs``: 63 rows per blob of the table MSM and one
+128-point transform over G1 (``batch.g1_fft``).  A caller that holds only the Lagrange half of the trusted setup gets
+the monomial points from ``g1_monomial_from_lagrange``.  ``install_cell_proofs(spec, proof_setup)`` puts the two
+functions in place of a spec module's own; ``install_cells`` and ``PUBLIC`` are what they were.
 """
 from __future__ import annotations
 
@@ -29,8 +35,12 @@ BYTES_PER_EXT_BLOB = CELLS_PER_EXT_BLOB * BYTES_PER_CELL
 ITEMS_MAX = 8192  # cells per verification call (128 columns x 64 blobs)
 BLOBS_MAX = 128   # blobs per cell-computation / recovery call
 
+PROOF_BLOBS_PER_MSM = 8  # blobs whose 63 rows share one table MSM of the proofs (504 of its 511 rows)
+
 PUBLIC = ("verify_cell_kzg_proof_batch", "compute_cells", "recover_cells")
+PUBLIC_PROOFS = ("compute_cells_and_kzg_proofs", "recover_cells_and_kzg_proofs")
 _SAVED = "_bls_mi355x_kzg_cells_saved"
+_SAVED_PROOFS = "_bls_mi355x_kzg_cell_proofs_saved"
 
 
 def _cell_bytes(cell) -> bytes:
@@ -213,6 +223,164 @@ def recover_cells_batch(cell_indices, cells_per_blob, ctx: _native.Context | Non
 
 def recover_cells(cell_indices, cells, ctx: _native.Context | None = None) -> list:
     return recover_cells_batch(cell_indices, [cells], ctx)[0]
+
+
+def g1_monomial_from_lagrange(g1_lagrange, ctx: _native.Context | None = None) -> list:
+    """KZG_SETUP_G1_MONOMIAL from KZG_SETUP_G1_LAGRANGE (4,096 points in the setup file's order, as ``KzgSetup``
+    takes them): the file's entry j is [L_j(tau)] with L_j the Lagrange basis at w^j (the spec bit-reverses the
+    list where it pairs it with a blob), and X^k = sum_j w^(j k) L_j, so [tau^k] = sum_j w^(j k) LAGRANGE[j] -- the
+    forward 4,096-point transform of the list as it stands, without 1 / n: one ``bls_g1_fft`` call."""
+    pts = [kzg._g1_bytes(p) for p in g1_lagrange]
+    if len(pts) != kzg.FIELD_ELEMENTS_PER_BLOB:
+        raise ValueError("the Lagrange setup has 4,096 G1 points")
+    try:
+        return batch.g1_fft(pts, ctx=ctx)
+    except ValueError:
+        raise ValueError("invalid point in the trusted setup") from None
+
+
+def _split_proofs(raw: bytes) -> list:
+    return [raw[48 * k: 48 * (k + 1)] for k in range(len(raw) // 48)]
+
+
+class CellProofSetup:
+    """The cell proof functions on one context.  ``cell_setup_or_ctx``: a ``CellSetup`` or ``kzg.KzgSetup`` (its
+    context, and its G1 table when it has one), a ``_native.Context``, or None for the default context.  Exactly
+    one of ``g1_monomial`` (KZG_SETUP_G1_MONOMIAL, 4,096 points) and ``g1_lagrange`` (KZG_SETUP_G1_LAGRANGE, 4,096
+    points, from which ``g1_monomial_from_lagrange`` derives the former).  The 4,096 points become entries of the
+    context's current G1 table -- found there as a consecutive run, or appended, which keeps a ``KzgSetup`` or
+    ``CellSetup`` on that table valid -- else of a table of their own (``self.table``), which replaces the
+    context's.  ``self.g1_monomial`` keeps the 4,096 encodings (the derived ones with ``g1_lagrange``)."""
+
+    def __init__(self, cell_setup_or_ctx, g1_monomial=None, g1_lagrange=None):
+        if (g1_monomial is None) == (g1_lagrange is None):
+            raise ValueError("give exactly one of g1_monomial and g1_lagrange")
+        given = list(g1_monomial if g1_monomial is not None else g1_lagrange)
+        if len(given) != kzg.FIELD_ELEMENTS_PER_BLOB:
+            raise ValueError("the cell proof setup takes 4,096 G1 points")
+        given = [kzg._g1_bytes(p) for p in given]
+        table = None
+        if isinstance(cell_setup_or_ctx, (CellSetup, kzg.KzgSetup)):
+            self.ctx = cell_setup_or_ctx.ctx
+            table = cell_setup_or_ctx.table
+        else:
+            self.ctx = cell_setup_or_ctx or _native.context()
+        pts = given if g1_monomial is not None else g1_monomial_from_lagrange(given, self.ctx)
+        if table is None and curve._g1_table is not None and curve._g1_table.ctx is self.ctx:
+            table = curve._g1_table
+        if table is not None and table._current():
+            first = table.run_of(pts)
+            if first is None:
+                first = len(table)
+                if not table.append(pts, subgroup_check=True).all():
+                    raise ValueError("invalid point in the trusted setup")
+        else:
+            table = batch.G1Table(self.ctx)
+            first = 0
+            if not table.load(pts, subgroup_check=True).all():
+                raise ValueError("invalid point in the trusted setup")
+        self.table, self.first, self.g1_monomial = table, first, pts
+        self.setup()
+
+    def setup(self) -> None:
+        """(again) name the table's entries to the library: after another object replaced and reloaded the table"""
+        c = self.ctx
+        if c.check(c.lib.bls_kzg_cell_proofs_setup(c.h, self.first, kzg.FIELD_ELEMENTS_PER_BLOB)) != 1:
+            raise ValueError("invalid point in the trusted setup")
+
+    def compute_cells_and_kzg_proofs_batch(self, blobs) -> list:
+        """[(cells, proofs)] per blob: 128 cells of 2,048 bytes and 128 proofs of 48 bytes"""
+        bl = [kzg._blob_bytes(b) for b in blobs]
+        for b in bl:
+            assert kzg.blob_is_canonical(b), "blob element not below the modulus"
+        c = self.ctx
+        out = []
+        for s in range(0, len(bl), BLOBS_MAX):
+            n = len(bl[s: s + BLOBS_MAX])
+            o = ctypes.create_string_buffer(BYTES_PER_EXT_BLOB * n)
+            pf = ctypes.create_string_buffer(48 * CELLS_PER_EXT_BLOB * n)
+            rc = c.check(c.lib.bls_kzg_compute_cells_and_proofs(c.h, b"".join(bl[s: s + n]), n, o, pf, None))
+            assert rc == 1, "blob element not below the modulus"
+            out += _cells_and_proofs(o.raw, pf.raw, n)
+        return out
+
+    def compute_cells_and_kzg_proofs(self, blob) -> tuple:
+        return self.compute_cells_and_kzg_proofs_batch([blob])[0]
+
+    def recover_cells_and_kzg_proofs_batch(self, cell_indices, cells_per_blob) -> list:
+        """[(cells, proofs)] of every blob from the same >= 64 present cells of each, as ``recover_cells_batch``
+        takes them"""
+        per_blob = [[_cell_bytes(x) for x in cells] for cells in cells_per_blob]
+        idx = None
+        for cells in per_blob:
+            idx = _recover_indices(cell_indices, len(cells))
+            for cell in cells:
+                assert kzg.blob_is_canonical(cell), "cell element not below the modulus"
+        if idx is None:
+            return []
+        c = self.ctx
+        a_idx = np.asarray(idx, dtype=np.uint32)
+        out = []
+        for s in range(0, len(per_blob), BLOBS_MAX):
+            n = len(per_blob[s: s + BLOBS_MAX])
+            o = ctypes.create_string_buffer(BYTES_PER_EXT_BLOB * n)
+            pf = ctypes.create_string_buffer(48 * CELLS_PER_EXT_BLOB * n)
+            rc = c.check(c.lib.bls_kzg_recover_cells_and_proofs(
+                c.h, a_idx.ctypes.data_as(ctypes.c_void_p), len(idx),
+                b"".join(b"".join(x) for x in per_blob[s: s + n]), n, o, pf, None))
+            assert rc == 1, "cell element not below the modulus"
+            out += _cells_and_proofs(o.raw, pf.raw, n)
+        return out
+
+    def recover_cells_and_kzg_proofs(self, cell_indices, cells) -> tuple:
+        return self.recover_cells_and_kzg_proofs_batch(cell_indices, [cells])[0]
+
+
+def _cells_and_proofs(cells_raw: bytes, proofs_raw: bytes, n: int) -> list:
+    pb = 48 * CELLS_PER_EXT_BLOB
+    return [(_split_cells(cells_raw[BYTES_PER_EXT_BLOB * i: BYTES_PER_EXT_BLOB * (i + 1)]),
+             _split_proofs(proofs_raw[pb * i: pb * (i + 1)])) for i in range(n)]
+
+
+def _check_sizes(spec) -> None:
+    if (int(getattr(spec, "FIELD_ELEMENTS_PER_CELL", 0)) != FIELD_ELEMENTS_PER_CELL
+            or int(getattr(spec, "CELLS_PER_EXT_BLOB", 0)) != CELLS_PER_EXT_BLOB):
+        raise ValueError("the device cell functions are built for FIELD_ELEMENTS_PER_CELL = 64 and "
+                         "CELLS_PER_EXT_BLOB = 128")
+
+
+def install_cell_proofs(spec, proof_setup: CellProofSetup) -> None:
+    """Replace ``compute_cells_and_kzg_proofs`` and ``recover_cells_and_kzg_proofs`` of a spec module object (the
+    sizes ``install_cells`` takes; any other is refused) with ``proof_setup``'s, each only where the module has that
+    name; cells and proofs come back as the module's own ``Cell`` and ``KZGProof`` types where it defines them."""
+    _check_sizes(spec)
+    if hasattr(spec, _SAVED_PROOFS):
+        uninstall_cell_proofs(spec)
+
+    def typed(result):
+        cells, proofs = result
+        return ([kzg._typed(spec, "Cell", x) for x in cells], [kzg._typed(spec, "KZGProof", x) for x in proofs])
+
+    new = {
+        "compute_cells_and_kzg_proofs": lambda blob: typed(proof_setup.compute_cells_and_kzg_proofs(blob)),
+        "recover_cells_and_kzg_proofs": lambda cell_indices, cells: typed(
+            proof_setup.recover_cells_and_kzg_proofs(cell_indices, cells)),
+    }
+    assert tuple(new) == PUBLIC_PROOFS
+    new = {name: fn for name, fn in new.items() if hasattr(spec, name)}
+    setattr(spec, _SAVED_PROOFS, {name: getattr(spec, name) for name in new})
+    for name, fn in new.items():
+        setattr(spec, name, fn)
+
+
+def uninstall_cell_proofs(spec) -> None:
+    """Put back what ``install_cell_proofs`` replaced."""
+    saved = getattr(spec, _SAVED_PROOFS, None)
+    if saved is None:
+        return
+    for name, old in saved.items():
+        setattr(spec, name, old)
+    delattr(spec, _SAVED_PROOFS)
 
 
 def install_cells(spec, cell_setup: CellSetup) -> None:

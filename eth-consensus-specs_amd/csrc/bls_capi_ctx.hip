@@ -318,6 +318,7 @@ void bls_ctx_destroy(bls_ctx* ctx) {
   if (ctx->kzc_tab) (void)hipFree(ctx->kzc_tab);
   if (ctx->kzc_negtau64) (void)hipFree(ctx->kzc_negtau64);
   if (ctx->kzc_idx) (void)hipFree(ctx->kzc_idx);
+  if (ctx->kp_idx) (void)hipFree(ctx->kp_idx);
   if (ctx->force_fb) (void)hipFree(ctx->force_fb);
   if (ctx->pc_stage) (void)hipHostFree(ctx->pc_stage);
   delete ctx;

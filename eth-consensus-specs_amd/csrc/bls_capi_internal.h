@@ -86,6 +86,11 @@ enum Slot {
   // per-item checks' selection and results, the interpolants' scalar rows and commitments
   S_KC_ENC, S_KC_CIDX, S_KC_KIDX, S_KC_P, S_KC_POK, S_KC_COK, S_KC_CF, S_KC_RFR, S_KC_PART, S_KC_RLI, S_KC_K, S_KC_S,
   S_KC_LIVE, S_KC_J, S_KC_SUM, S_KC_SEED, S_KC_PP, S_KC_PQ, S_KC_FV, S_KC_SEL, S_KC_RES, S_KC_ROWS, S_KC_I,
+  // cell proofs and the G1 transform (bls_capi_kzg_cells.hip): the uploaded encodings, the decoded points and their
+  // verdicts, the scalar rows of one table MSM, the transform's buffer (the h_m of every blob: an MSM's results are
+  // copied out of the S_G1M_* slots before the next one), the buffer in output order, its live flags, affine forms
+  // and encodings
+  S_KP_IN, S_KP_A, S_KP_OK, S_KP_ROWS, S_KP_BUF, S_KP_PERM, S_KP_LIVE, S_KP_AFF, S_KP_OUT,
   NSLOT
 };
 
@@ -229,6 +234,10 @@ struct bls_ctx {
   uint32_t* kzc_idx = nullptr;
   bool kzc_set = false;
   uint64_t kzc_gen = 0;
+  // ... the cell proof setup: the device list of the 4,096 table indices of [tau^i] G1 and the table generation
+  uint32_t* kp_idx = nullptr;
+  bool kp_set = false;
+  uint64_t kp_gen = 0;
   Job* work_job = nullptr;  // the job whose bits batch bls_last_gather_work reports
   // test hook (bls_test_force_h2c_fallback): items whose hash_to_G2 is routed to k_h2c_fallback regardless of
   // the lane kernels' flags; null in every product use

@@ -268,6 +268,23 @@ hipError_t launch_cells_item_pairs(hipStream_t st, size_t nc, size_t n, const G1
                                    const uint32_t* kidx, const G1A* I, const Fr* W, const G2A* negtau64, G1A* P,
                                    G2A* Q);
 
+// The transform over G1 and the cell proofs' rows (bls_g1_fft.hip; pieces and derivation: bls_g1_fft.h).  buf: B
+// vectors of 2^logn canonical projective points (1 <= logn <= 12), W: launch_ntt_tables' table.
+// launch_g1fft_load: vector v's entries 0 .. have are src[v have ..] (the identity where live, nullable, is 0), the
+// rest the identity.  launch_g1fft: logn stages in place, natural order in, bit-reversed order out; the inverse
+// includes 1 / n.  launch_g1fft_finish: out = buf in bit-reversed (as it stands) or natural order, live, aff and
+// out48 its B 2^logn live flags, affine forms and encodings
+hipError_t launch_g1fft_load(hipStream_t st, const G1A* src, const int* live, uint32_t have, uint32_t logn, size_t B,
+                             G1P* buf);
+hipError_t launch_g1fft(hipStream_t st, const Fr* W, uint32_t logn, bool inverse, size_t B, G1P* buf);
+hipError_t launch_g1fft_finish(hipStream_t st, const G1P* buf, uint32_t logn, size_t B, bool natural, G1P* out,
+                               int* live, G1A* aff, uint8_t* out48);
+// rows32: per blob 63 rows of 4,032 32-byte big-endian scalars, row m = coef[64 (m + 1) + i], zero from 4,096 on
+// (coef: 4,096 Montgomery elements per blob)
+size_t cellproof_rows_per_blob();
+size_t cellproof_row_entries();
+hipError_t launch_cellproof_rows(hipStream_t st, const Fr* coef, size_t B, uint8_t* rows32);
+
 // wavefront-cooperative arithmetic (bls_wide.hip)
 hipError_t launch_wide_selftest(hipStream_t st, size_t nw, const uint8_t* be48, int* bad);
 // hash_to_G2 with one wave per message (msgs 32 B apart when offs is null); flag[i] = 1: recompute on the fallback;

@@ -461,6 +461,46 @@ int bls_kzg_compute_cells(bls_ctx* ctx, const uint8_t* blobs, size_t B, uint8_t*
  * the spec's algorithm yields on them. */
 int bls_kzg_recover_cells(bls_ctx* ctx, const uint32_t* cell_index, size_t n_present, const uint8_t* cells, size_t B,
                           uint8_t* out_cells, uint8_t* out_ok);
+/* The radix-2 transform over G1, out[k] = sum_i [w_n^(i k)] in[i] with w_n the
+ * n-th root of unity of the cell functions' domain (w_n = w^(8192 / n), w =
+ * 7^((r - 1) / 8192)), for B >= 1 independent vectors of n = 2^k points, 2 <= n
+ * <= 4,096: vector v is the n compressed points at in48 + 48 n v, and its
+ * transform goes to out48 + 48 n v.  Input and output are in natural order.
+ * inverse != 0 takes w_n^-1 and includes the factor 1 / n.  The identity
+ * (c0 00...) is a valid point anywhere.  Returns 1 on success; 0 if an
+ * encoding is invalid or not in G1 (out48 is not written); BLS_E_ARG if n is
+ * not a power of two in 2 .. 4,096, B == 0 or n B > 2^20.  One kernel launch
+ * per stage, one lane per butterfly over all B vectors. */
+int bls_g1_fft(bls_ctx* ctx, const uint8_t* in48, size_t n, size_t B, int inverse, uint8_t* out48);
+/* ---- Fulu cell proofs (compute_cells_and_kzg_proofs, recover_cells_and_kzg_proofs) -- */
+/* bls_kzg_cell_proofs_setup: monomial_n = 4,096 names entries monomial_first ..
+ * monomial_first + 4,096 of the resident G1 table as KZG_SETUP_G1_MONOMIAL
+ * ([tau^i] G1).  Returns 1; 0 if a named entry is invalid; BLS_E_NOREG without
+ * a table; BLS_E_ARG if the entries are out of range or monomial_n is not
+ * 4,096.  It remembers bls_g1_table_generation as bls_kzg_cells_setup does: the
+ * two calls below return BLS_E_NOREG without this setup and BLS_E_ARG after the
+ * table has been replaced, until the setup is made again.  It is independent
+ * of bls_kzg_cells_setup (proofs need no G2 point), and bls_g1_table_append
+ * keeps both valid.
+ *
+ * bls_kzg_compute_cells_and_proofs: bls_kzg_compute_cells (same arguments,
+ * checks, cell bytes, out_ok and return value; cells may be NULL here) and the
+ * 128 proofs of every blob, 48 bytes each in cell order at proofs48 + 6144 b.
+ * With p = sum f_i X^i the blob's polynomial, the proof of cell k is
+ *   pi_k = sum_{m < 64} [a_k^m] h_m,  a_k = w_128^brp7(k),
+ *   h_m = sum_{i < 4096 - 64 (m + 1)} f_{i + 64 (m + 1)} [tau^i] G1
+ * the h_m being 63 rows per blob of the table MSM (bls_g1_table_msm's kernels;
+ * zero scalars cost nothing there) and the pi_k one 128-point bls_g1_fft over
+ * all blobs.  A blob that is not ok gets 128 x 48 zero bytes.
+ *
+ * bls_kzg_recover_cells_and_proofs: bls_kzg_recover_cells (same arguments,
+ * checks, cell bytes, out_ok and return value) and the proofs of the recovered
+ * polynomial as above. */
+int bls_kzg_cell_proofs_setup(bls_ctx* ctx, uint32_t monomial_first, uint32_t monomial_n);
+int bls_kzg_compute_cells_and_proofs(bls_ctx* ctx, const uint8_t* blobs, size_t B, uint8_t* cells, uint8_t* proofs48,
+                                     uint8_t* out_ok);
+int bls_kzg_recover_cells_and_proofs(bls_ctx* ctx, const uint32_t* cell_index, size_t n_present, const uint8_t* cells,
+                                     size_t B, uint8_t* out_cells, uint8_t* out_proofs48, uint8_t* out_ok);
 /* GT.multi_pairing: prod_i e(P_i, Q_i) after the final exponentiation, as 576
  * bytes (six Fp2 coefficients c0..c5 of the w-basis, each c0||c1 big-endian;
  * GT one = byte 47 set).  n == 0 gives one. */
