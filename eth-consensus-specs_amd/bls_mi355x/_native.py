@@ -120,6 +120,8 @@ _SIGS = {
     "bls_g1_table_generation": (ctypes.c_uint64, [_vp]),
     "bls_g1_table_msm": (_ip, [_vp, _vp, _sz, _vp, _sz, _vp]),
     "bls_g1_table_stats": (_ip, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "bls_g1_msm": (_ip, [_vp, _u8p, _sz, _u8p, _sz, _ip, _vp]),
+    "bls_g1_msm_stats": (_ip, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "bls_kzg_setup": (_ip, [_vp, _u8p, ctypes.c_uint32, ctypes.c_uint32]),
     "bls_kzg_eval_blobs": (_ip, [_vp, _u8p, _sz, _u8p, _vp, _vp]),
     "bls_kzg_blob_commitments": (_ip, [_vp, _u8p, _sz, _vp, _vp]),

@@ -784,6 +784,43 @@ def g1_table_stats(ctx=None) -> tuple[int, int, int]:
     return int(calls.value), int(entries.value), int(getattr(c, "g1_decode_hits", 0))
 
 
+def g1_msm(points48, scalar_rows, subgroup_check: bool = False, ctx=None) -> list:
+    """B linear combinations over the call's own points in one call (``bls_g1_msm``, a bucket MSM without a resident
+    table): result[v] = sum_i [scalar_rows[v][i]] P_i, 48 compressed bytes each.  Points are 48-byte encodings,
+    decoded without the subgroup check unless asked; scalars are ints 0 <= k < 2^256, one per point in every row.
+    They are passed as given and taken as integer multiples, like ``g1_lincomb_batch``'s (no reduction mod r here:
+    for the reduced form that the reference's Scalar gives, use ``g1_multi_exp``, or reduce first).  Raises ValueError
+    on an empty input (the reference raises on an empty multi_exp) and on an invalid encoding or, with
+    ``subgroup_check``, a point outside G1."""
+    c = ctx or _native.context()
+    pts = [bytes(p) for p in points48]
+    if not pts:
+        raise ValueError("Cannot call multi_exp with zero points or zero scalars")
+    if any(len(p) != 48 for p in pts):
+        raise ValueError("need 48-byte points and 256-bit scalars")
+    n = len(pts)
+    rows = _lincomb_rows(scalar_rows, n)
+    B = len(rows) // (32 * n)
+    if B == 0:
+        raise ValueError("Cannot call multi_exp with zero points or zero scalars")
+    out = ctypes.create_string_buffer(48 * B)
+    rc = c.lib.bls_g1_msm(c.h, b"".join(pts), n, rows, B, 1 if subgroup_check else 0, out)
+    if rc == _native.BLS_E_ARG:
+        raise ValueError("too many rows or scalars for one call")
+    if c.check(rc) != 1:
+        raise ValueError("invalid G1 point encoding")
+    return [out.raw[48 * v: 48 * v + 48] for v in range(B)]
+
+
+def g1_msm_stats(ctx=None) -> tuple[int, int]:
+    """(``g1_msm`` calls that ran, bucket entries their sorts placed) since the context was created
+    (``bls_g1_msm_stats``): which route ran, and how many non-zero digits of non-identity points it saw."""
+    c = ctx or _native.context()
+    calls, entries = ctypes.c_uint64(), ctypes.c_uint64()
+    c.check(c.lib.bls_g1_msm_stats(c.h, ctypes.byref(calls), ctypes.byref(entries)))
+    return int(calls.value), int(entries.value)
+
+
 def g1_fft(points, inverse: bool = False, ctx=None):
     """The radix-2 transform over G1 on the device (``bls_g1_fft``): out[k] = sum_i [w_n^(i k)] points[i], w_n the
     n-th root of unity of the cell functions' domain, in natural order on both sides; ``inverse`` takes w_n^-1 and

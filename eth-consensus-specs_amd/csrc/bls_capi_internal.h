@@ -91,6 +91,11 @@ enum Slot {
   // copied out of the S_G1M_* slots before the next one), the buffer in output order, its live flags, affine forms
   // and encodings
   S_KP_IN, S_KP_A, S_KP_OK, S_KP_ROWS, S_KP_BUF, S_KP_PERM, S_KP_LIVE, S_KP_AFF, S_KP_OUT,
+  // bucket MSM over a call's own points (bls_g1_msm, bls_capi_msm.hip): the scalars and encodings, the decoded points
+  // and verdicts, their records and live flags, the sort's counters, offsets and lists, the fold's two partial
+  // arrays, the bit sums, the window sums and their flags, the results (projective, live, affine), the output bytes
+  S_GV_IN, S_GV_A, S_GV_OK, S_GV_REC, S_GV_PLIVE, S_GV_U32, S_GV_PA, S_GV_PB, S_GV_U, S_GV_W, S_GV_WLIVE, S_GV_RES,
+  S_GV_LIVE, S_GV_AFF, S_GV_OUT,
   NSLOT
 };
 
@@ -217,6 +222,7 @@ struct bls_ctx {
   size_t g1t_n = 0, g1t_cap = 0;
   bool g1t_checked = false;
   uint64_t g1t_gen = 0, g1t_msm_calls = 0, g1t_msm_entries = 0;
+  uint64_t g1v_msm_calls = 0, g1v_msm_entries = 0;  // bls_g1_msm_stats: the bucket MSMs over a call's own points
   // blob KZG (bls_capi_kzg.hip): the domain table omega^brp(i), filled on first use; the setup's -[tau] G2 and, with
   // a Lagrange setup, the device list of its 4,096 table indices kzg_first + i and the G1 table generation it was
   // made on (a commitment call after the table was replaced is refused, the committee table's rule)
@@ -287,6 +293,12 @@ hipError_t launch_pairs_decode(hipStream_t st, const uint8_t* d_in, size_t n, bo
 hipError_t launch_miller_call(hipStream_t st, const G1A* P, const G2A* Q, size_t n, Fp12* f, size_t* nf,
                               const Fp2* qz);
 int stage_pairs(bls_ctx* ctx, const uint8_t* g1s48, const uint8_t* g2s96, size_t n, bool subgroup, G1A** P, G2A** Q);
+// The bucket MSM over device-resident points (bls_capi_msm.hip; launch_g1_var_msm on the job's stream with the
+// S_GV_* scratch): aff / live[v] = sum_i [k32[v n + i]] pts[i] for v < B, in the caller's arrays; out48 (nullable,
+// device): the compressed bytes; *d_entries (nullable): where the device leaves the bucket entries.  No host round
+// trip; counted by bls_g1_msm_stats as one call (the entries only where the caller reads them back).
+int g1_var_msm_dev(bls_ctx* ctx, const G1A* pts, const int* ok, size_t n, size_t B, const uint8_t* k32, G1A* aff,
+                   int* live, uint8_t* out48, const uint32_t** d_entries);
 int ensure_comb(bls_ctx* ctx, hipStream_t st);  // ctx->comb, the -G1 comb (bls_bisect.hip), built on first use
 int host_seed(bls_ctx* ctx, uint8_t seed[32]);
 int nccl_fail(bls_ctx* c, ncclResult_t r, const char* where);

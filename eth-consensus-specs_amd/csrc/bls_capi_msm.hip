@@ -4,6 +4,7 @@
 constexpr size_t G1T_MAX = (size_t)1 << 26;  // entries: a record number 32 cap + i fits 32 bits
 constexpr int G1T_WINDOWS = 32;
 constexpr size_t G1M_BMAX = 65536;           // vectors per call: 256 B bucket slots fit 24 bits
+constexpr size_t G1VM_BMAX = 256;            // rows per bls_g1_msm call: 8,192 B bucket slots (2^21), five words each
 
 // Decode n encodings into entries first .. first + n (records of all 32 windows, state bytes on both sides).
 static int g1t_fill(bls_ctx* ctx, const uint8_t* pts48, size_t n, size_t first, int subgroup, uint8_t* out_ok) {
@@ -32,6 +33,28 @@ static int g1t_fill(bls_ctx* ctx, const uint8_t* pts48, size_t n, size_t first, 
 static int g1t_alloc(bls_ctx* ctx, size_t cap, RegKey** tab, uint8_t** stat) {
   HIPCK(hipMalloc(tab, cap * G1T_WINDOWS * sizeof(RegKey)));
   HIPCK(hipMalloc(stat, cap));
+  return 0;
+}
+
+int capi::g1_var_msm_dev(bls_ctx* ctx, const G1A* pts, const int* ok, size_t n, size_t B, const uint8_t* k32,
+                         G1A* aff, int* live, uint8_t* out48, const uint32_t** d_entries) {
+  const G1MsmPlan p = g1_var_msm_plan(n, B);
+  uint32_t* d_u32;
+  RegKey* d_rec;
+  G1P *d_pa, *d_pb, *d_u, *d_w, *d_res;
+  int *d_plive, *d_wlive;
+  SCR(S_GV_REC, n, d_rec);
+  SCR(S_GV_PLIVE, n, d_plive);
+  SCR(S_GV_U32, p.u32_words, d_u32);
+  SCR(S_GV_PA, p.part[0], d_pa);
+  SCR(S_GV_PB, p.part[1], d_pb);
+  SCR(S_GV_U, 8 * G1T_WINDOWS * B, d_u);
+  SCR(S_GV_W, G1T_WINDOWS * B, d_w);
+  SCR(S_GV_WLIVE, G1T_WINDOWS * B, d_wlive);
+  SCR(S_GV_RES, B, d_res);
+  HIPCK(launch_g1_var_msm(ctx->j->stream, p, pts, ok, (uint32_t)n, (uint32_t)B, k32, d_rec, d_plive, d_u32, d_pa,
+                          d_pb, d_u, d_w, d_wlive, d_res, live, aff, out48, d_entries));
+  ctx->g1v_msm_calls++;
   return 0;
 }
 
@@ -138,6 +161,45 @@ int bls_g1_table_msm(bls_ctx* ctx, const uint32_t* idx, size_t n, const uint8_t*
   ctx->g1t_msm_calls++;
   ctx->g1t_msm_entries += entries;
   return 1;
+}
+
+int bls_g1_msm(bls_ctx* ctx, const uint8_t* pts48, size_t n, const uint8_t* scalars32, size_t B, int subgroup_check,
+               uint8_t* out48) {
+  API_ENTER(ctx);
+  if ((n && (!pts48 || !scalars32)) || !out48 || !B || B > G1VM_BMAX) return BLS_E_ARG;
+  if (n >= ((size_t)1 << 31) || B * n * G1T_WINDOWS >= ((size_t)1 << 31)) return BLS_E_ARG;
+  if (!n) return 0;  // the reference raises on an empty input, as bls_multi_exp
+  hipStream_t st = ctx->j->stream;
+  uint8_t *d_in, *d_out;
+  G1A *d_a, *d_aff;
+  int *d_ok, *d_live;
+  const size_t kbytes = 32 * n * B;  // the scalars first: the sort reads them 16 bytes at a time
+  SCR(S_GV_IN, kbytes + 48 * n, d_in);
+  SCR(S_GV_A, n, d_a);
+  SCR(S_GV_OK, n, d_ok);
+  SCR(S_GV_LIVE, B, d_live);
+  SCR(S_GV_AFF, B, d_aff);
+  SCR(S_GV_OUT, 48 * B, d_out);
+  CK(h2d(ctx, d_in, scalars32, kbytes));
+  CK(h2d(ctx, d_in + kbytes, pts48, 48 * n));
+  HIPCK(launch_pt_decode(st, 1, d_in + kbytes, n, subgroup_check ? 1 : 0, d_a, d_ok));
+  const int v = all_ok(ctx, d_ok, n);
+  if (v <= 0) return v;
+  const uint32_t* d_entries = nullptr;
+  CK(g1_var_msm_dev(ctx, d_a, d_ok, n, B, d_in, d_aff, d_live, d_out, &d_entries));
+  uint32_t entries = 0;
+  HIPCK(hipMemcpyAsync(&entries, d_entries, sizeof entries, hipMemcpyDeviceToHost, st));
+  CK(d2h(ctx, out48, d_out, 48 * B));
+  ctx->g1v_msm_entries += entries;
+  return 1;
+}
+
+int bls_g1_msm_stats(bls_ctx* ctx, uint64_t* calls, uint64_t* bucket_entries) {
+  if (!ctx) return BLS_E_ARG;
+  std::lock_guard<std::mutex> lock_(ctx->mu);
+  if (calls) *calls = ctx->g1v_msm_calls;
+  if (bucket_entries) *bucket_entries = ctx->g1v_msm_entries;
+  return 0;
 }
 
 int bls_g1_table_stats(bls_ctx* ctx, uint64_t* msm_calls, uint64_t* bucket_entries) {

@@ -17,8 +17,15 @@
 //                   lane, then a 6-level LDS tree (k_msm_usum's scheme)
 //   k_g1m_final     sum_b 2^b U_{v,b} by Horner, one lane per vector; launch_g1_affine; k_g1m_compress
 // The scan is three kernels over blocks of 1,024 counters, so 256 B slots need no single-block limit.
+//
+// Variable base (launch_g1_var_msm), out[v] = sum_i [k_{v,i}] P_i over the call's own points, no window multiples:
+//   k_g1vm_records  the n points as single-window records
+//   k_g1vm_sort (count) / scan / k_g1vm_sort (scatter)   buckets per (row, window, digit): 8,192 B slots
+//   the levels, k_g1m_usum and k_g1m_final above over the 32 B slot groups: one window sum W_{v,w} per (row, window)
+//   k_g1vm_combine  sum_w 2^(8w) W_{v,w} by Horner from the row's top window, one lane per row; launch_g1_affine;
+//                   k_g1m_compress
 #include "bls_kernels.h"
-#include "bls_g1_msm.h"
+#include "bls_g1_var_msm.h"
 #include "bls_key_out.h"
 
 namespace bls {
@@ -259,6 +266,37 @@ G1MsmPlan g1_msm_plan(size_t n, size_t B) {
   return p;
 }
 
+// The levelled bucket sums, the bit sums and Horner over G slot groups of 256 slots each (N = 256 G; a group is a
+// vector of the table MSM, a (row, window) of the variable-base one): res[g] = sum_d d S_{g,d}, live[g] = res[g] is
+// not the identity.  offA: the lists' offsets, lst: their record numbers into tab.
+static hipError_t g1m_reduce(hipStream_t st, const G1MsmPlan& p, uint32_t N, uint32_t G, const RegKey* tab,
+                             const uint32_t* lst, uint32_t* cnt, const uint32_t* offA, uint32_t* const offL[2],
+                             uint32_t* bsum, G1P* const part[2], G1P* U, G1P* res, int* live) {
+  hipError_t e;
+  // level l cuts the items at ioff (the lists, then the partials of level l - 1) into the runs at roff
+  const uint32_t* ioff = offA;
+  const G1P* sums = nullptr;
+  for (int l = 0; l < p.levels; ++l) {
+    uint32_t* roff = offL[l & 1];
+    G1P* out = part[l & 1];
+    hipLaunchKernelGGL(k_g1m_nruns, dim3(nblk(N, 256)), dim3(256), 0, st, ioff, N, cnt);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = g1m_scan(st, cnt, N, roff, bsum, nullptr)) != hipSuccess) return e;
+    const unsigned fb = nblk(p.level_runs[l], 64);
+    if (l == 0)
+      hipLaunchKernelGGL(k_g1m_fold<true>, dim3(fb), dim3(64), 0, st, ioff, roff, N, tab, lst, nullptr, out);
+    else
+      hipLaunchKernelGGL(k_g1m_fold<false>, dim3(fb), dim3(64), 0, st, ioff, roff, N, nullptr, nullptr, sums, out);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    ioff = roff;
+    sums = out;
+  }
+  hipLaunchKernelGGL(k_g1m_usum, dim3(8 * G), dim3(64), 0, st, ioff, sums, U);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_g1m_final, dim3(nblk(G, 64)), dim3(64), 0, st, U, G, res, live);
+  return hipGetLastError();
+}
+
 hipError_t launch_g1_table_msm(hipStream_t st, const G1MsmPlan& p, const RegKey* tab, uint32_t cap,
                                const uint8_t* stat, const uint32_t* idx, uint32_t n, uint32_t B, const uint8_t* k32,
                                uint32_t* scr, G1P* partA, G1P* partB, G1P* U, G1P* res, int* live, G1A* aff,
@@ -280,29 +318,103 @@ hipError_t launch_g1_table_msm(hipStream_t st, const G1MsmPlan& p, const RegKey*
   hipLaunchKernelGGL(k_g1m_sort<true>, dim3(sb), dim3(256), 0, st, idx, stat, n, B, k32, cap, cur, lst);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   *d_entries = offA + N;  // the entries the buckets hold
-  // level l cuts the items at ioff (the lists, then the partials of level l - 1) into the runs at roff
-  const uint32_t* ioff = offA;
-  const G1P* sums = nullptr;
-  for (int l = 0; l < p.levels; ++l) {
-    uint32_t* roff = offL[l & 1];
-    G1P* out = part[l & 1];
-    hipLaunchKernelGGL(k_g1m_nruns, dim3(nblk(N, 256)), dim3(256), 0, st, ioff, N, cnt);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = g1m_scan(st, cnt, N, roff, bsum, nullptr)) != hipSuccess) return e;
-    const unsigned fb = nblk(p.level_runs[l], 64);
-    if (l == 0)
-      hipLaunchKernelGGL(k_g1m_fold<true>, dim3(fb), dim3(64), 0, st, ioff, roff, N, tab, lst, nullptr, out);
-    else
-      hipLaunchKernelGGL(k_g1m_fold<false>, dim3(fb), dim3(64), 0, st, ioff, roff, N, nullptr, nullptr, sums, out);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    ioff = roff;
-    sums = out;
+  if ((e = g1m_reduce(st, p, N, B, tab, lst, cnt, offA, offL, bsum, part, U, res, live)) != hipSuccess) return e;
+  if ((e = launch_g1_affine(st, B, live, res, aff)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_g1m_compress, dim3(nblk(B, 64)), dim3(64), 0, st, aff, B, out48);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------- variable base (bls_g1_msm) --
+// The call's own points (per-lane pieces in bls_g1_var_msm.h): record i = point i (REG_VALID and live[i] set on a
+// usable non-identity point), one window only.
+__global__ void __launch_bounds__(256) k_g1vm_records(const G1A* a, const int* ok, uint32_t n, RegKey* rec,
+                                                      int* live) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const G1A p = a[i];
+  const bool pt = ok[i] != 0 && !p.inf;
+  KeyOutRecords{rec, nullptr}.put(i, p, pt ? 1 : 0);
+  live[i] = pt ? 1 : 0;
+}
+
+// k_g1m_sort's two passes with buckets per (row, window, digit): one lane per (v, i); the non-zero digit d of window w
+// goes to slot (v * 32 + w) * 256 + d as record number i.  Points that are not live are dropped.
+template <bool SCATTER>
+__global__ void __launch_bounds__(256) k_g1vm_sort(const int* live, uint32_t n, uint32_t B, const uint8_t* k32,
+                                                   uint32_t* cnt_or_cur, uint32_t* lst) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)n * B) return;
+  const uint32_t v = (uint32_t)(t / n), i = (uint32_t)(t % n);
+  if (!live[i]) return;
+  uint32_t k[8];
+  {
+    const uint4* p = reinterpret_cast<const uint4*>(k32 + 32 * t);
+    const uint4 lo = p[0], hi = p[1];
+    k[0] = lo.x, k[1] = lo.y, k[2] = lo.z, k[3] = lo.w, k[4] = hi.x, k[5] = hi.y, k[6] = hi.z, k[7] = hi.w;
   }
-  hipLaunchKernelGGL(k_g1m_usum, dim3(8 * B), dim3(64), 0, st, ioff, sums, U);
+  g1vm_each_slot(k, v, [&](uint32_t slot) {
+    if (SCATTER) lst[atomicAdd(&cnt_or_cur[slot], 1u)] = i;
+    else atomicAdd(&cnt_or_cur[slot], 1u);
+  });
+}
+
+// res[v] = sum_w 2^(8w) W[32 v + w], one lane per row (g1vm_combine); live[v] = 0 for the identity
+__global__ void __launch_bounds__(64) k_g1vm_combine(const G1P* W, uint32_t B, G1P* res, int* live) {
+  const uint32_t v = blockIdx.x * 64 + threadIdx.x;
+  if (v >= B) return;
+  const G1P o = g1m_pack(g1vm_combine(W + (size_t)G1M_WINDOWS * v));
+  res[v] = o;
+  live[v] = fp_is_zero(o.z) ? 0 : 1;
+}
+
+G1MsmPlan g1_var_msm_plan(size_t n, size_t B) {
+  G1MsmPlan p{};
+  const size_t groups = B * G1M_WINDOWS;
+  p.slots = (uint32_t)(groups * G1M_SLOTS);
+  p.entries = n * groups;
+  size_t deepest = n, total = p.entries;  // a bucket holds at most every point once
+  do {
+    deepest = (deepest + G1M_K - 1) / G1M_K;
+    // one partly filled run per non-empty bucket, and never more runs than items
+    const size_t runs = (total + G1M_K - 1) / G1M_K + (size_t)255 * groups;
+    total = runs < total ? runs : total;
+    size_t& part = p.part[p.levels & 1];
+    part = total > part ? total : part;
+    p.level_runs[p.levels++] = total;
+  } while (deepest > 1);
+  if (!p.part[1]) p.part[1] = 1;
+  p.u32_words = (size_t)5 * p.slots + 3 + nblk(p.slots, SCAN_BLK) + 1 + p.entries;
+  return p;
+}
+
+hipError_t launch_g1_var_msm(hipStream_t st, const G1MsmPlan& p, const G1A* pts, const int* ok, uint32_t n,
+                             uint32_t B, const uint8_t* k32, RegKey* rec, int* plive, uint32_t* scr, G1P* partA,
+                             G1P* partB, G1P* U, G1P* W, int* wlive, G1P* res, int* live, G1A* aff, uint8_t* out48,
+                             const uint32_t** d_entries) {
+  const uint32_t N = p.slots, G = B * G1M_WINDOWS;
+  uint32_t* cnt = scr;
+  uint32_t* cur = cnt + N;
+  uint32_t* offA = cur + N;
+  uint32_t* offL[2] = {offA + N + 1, offA + 2 * (size_t)N + 2};
+  uint32_t* bsum = offA + 3 * (size_t)N + 3;
+  uint32_t* lst = bsum + nblk(N, SCAN_BLK) + 1;
+  G1P* part[2] = {partA, partB};
+  hipError_t e;
+  hipLaunchKernelGGL(k_g1vm_records, dim3(nblk(n, 256)), dim3(256), 0, st, pts, ok, n, rec, plive);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_g1m_final, dim3(nblk(B, 64)), dim3(64), 0, st, U, B, res, live);
+  if ((e = hipMemsetAsync(cnt, 0, (size_t)N * sizeof(uint32_t), st)) != hipSuccess) return e;
+  const unsigned sb = nblk((size_t)n * B, 256);
+  hipLaunchKernelGGL(k_g1vm_sort<false>, dim3(sb), dim3(256), 0, st, plive, n, B, k32, cnt, nullptr);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = g1m_scan(st, cnt, N, offA, bsum, cur)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_g1vm_sort<true>, dim3(sb), dim3(256), 0, st, plive, n, B, k32, cur, lst);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (d_entries) *d_entries = offA + N;
+  if ((e = g1m_reduce(st, p, N, G, rec, lst, cnt, offA, offL, bsum, part, U, W, wlive)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_g1vm_combine, dim3(nblk(B, 64)), dim3(64), 0, st, W, B, res, live);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if ((e = launch_g1_affine(st, B, live, res, aff)) != hipSuccess) return e;
+  if (!out48) return hipSuccess;
   hipLaunchKernelGGL(k_g1m_compress, dim3(nblk(B, 64)), dim3(64), 0, st, aff, B, out48);
   return hipGetLastError();
 }

@@ -200,6 +200,17 @@ hipError_t launch_g1_table_msm(hipStream_t st, const G1MsmPlan& p, const RegKey*
                                const uint8_t* stat, const uint32_t* idx, uint32_t n, uint32_t B, const uint8_t* k32,
                                uint32_t* scr, G1P* partA, G1P* partB, G1P* U, G1P* res, int* live, G1A* aff,
                                uint8_t* out48, const uint32_t** d_entries);
+// The bucket MSM over a call's own points (bls_g1_var_msm.h): res / aff / out48[v] = sum_i [k32[v n + i]] pts[i],
+// v < B, integer multiples.  pts / ok: n decoded points and their usability flags (a point with ok = 0 is dropped like
+// the identity: the caller refuses invalid encodings first); k32 16-byte aligned.  The plan has 8,192 B slots and a
+// fullest bucket of n entries.  rec: n records, plive: n; scr / partA / partB as the plan says; U: 256 B, W: 32 B G1P,
+// wlive: 32 B; res: B G1P (canonical projective), live: B (0 for the identity), aff: B G1A; out48 (nullable): the
+// compressed bytes; d_entries (nullable) as above.  Everything stays on the device and on st.
+G1MsmPlan g1_var_msm_plan(size_t n, size_t B);
+hipError_t launch_g1_var_msm(hipStream_t st, const G1MsmPlan& p, const G1A* pts, const int* ok, uint32_t n,
+                             uint32_t B, const uint8_t* k32, RegKey* rec, int* plive, uint32_t* scr, G1P* partA,
+                             G1P* partB, G1P* U, G1P* W, int* wlive, G1P* res, int* live, G1A* aff, uint8_t* out48,
+                             const uint32_t** d_entries);
 
 // Deneb blob KZG on F_r (bls_kzg.hip; lane pieces bls_kzg_blob.h, field bls_fr.h).  Fr: 32 B, Montgomery form.
 // dom: the 4,096 domain entries omega^brp(i) (kzg_domain_bytes()); f: 4,096 elements per blob; ok[b] = every element

@@ -348,6 +348,24 @@ int bls_g1_table_msm(bls_ctx* ctx, const uint32_t* idx, size_t n, const uint8_t*
  * the bucket entries (non-zero digits of non-identity entries) they added.
  * Returns 0. */
 int bls_g1_table_stats(bls_ctx* ctx, uint64_t* msm_calls, uint64_t* bucket_entries);
+/* ---- bucket MSM over a call's own G1 points (variable base) --------------- */
+/* out48[v] = sum_i [k_{v,i}] P_i for v < B: n compressed points, decoded as
+ * bls_multi_exp decodes them (identity accepted, subgroup check on request),
+ * and a B x n matrix of 32-byte big-endian scalars (row v at
+ * scalars32 + 32 n v), any 0 <= k < 2^256 taken as an integer multiple and not
+ * reduced mod r: for a point decoded without the subgroup check the result is
+ * the bytes bls_multi_exp gives.  Always the bucket path (digit sort per (row,
+ * window), bucket folds, one doubling chain per row), from n = 1: callers
+ * choose between this and bls_multi_exp.  Returns 1; 0 for an invalid
+ * encoding, a point outside G1 under subgroup_check, or n == 0 (the reference
+ * raises on an empty input); BLS_E_ARG for null pointers, B == 0, B > 256 or
+ * 32 B n >= 2^31. */
+int bls_g1_msm(bls_ctx* ctx, const uint8_t* pts48, size_t n, const uint8_t* scalars32, size_t B, int subgroup_check,
+               uint8_t* out48);
+/* Totals since the context was created: bucket MSMs over a call's own points
+ * that ran and the bucket entries (non-zero digits of non-identity points)
+ * their sorts placed.  Returns 0. */
+int bls_g1_msm_stats(bls_ctx* ctx, uint64_t* calls, uint64_t* bucket_entries);
 /* ---- Deneb blob KZG on the device (specs/deneb/polynomial-commitments.md) -- */
 /* A blob is 4,096 field elements of 32 big-endian bytes (131,072 bytes), the
  * evaluations of a polynomial p over the bit-reversed 4,096th roots of unity;
